@@ -7,6 +7,7 @@ gloo as the bootstrap and the library's own communicator paths forced on over th
 (SELAVI_NATIVE_COMM=force, SELAVI_RCCL_LIB): the WHOLE script -- data-parallel step with SyncBN + gradient buckets, the
 preflight watchdog, forward timing, row-sharded SK through slv_sk_iterate_sharded, the cfg5 bf16 leg under data
 parallelism, max-over-ranks timing, ONE JSON line from rank 0 -- runs as the driver will run it.
+The tests add --full, which runs those side measurements after the headline.
 Reference wiring: /root/reference/main.py:117-118,156-160, utils.py:133-146."""
 import json
 import os
@@ -69,7 +70,7 @@ def test_driver_scale_command_two_ranks_on_one_gpu(transport):
     port = 24100 + os.getpid() % 500 + (0 if transport == "native_double" else 500)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--cfg5-batch", "16", "--cfg5-steps", "2", "--cfg5-warmup", "1"]
+           "--full", "--cfg5-batch", "16", "--cfg5-steps", "2", "--cfg5-warmup", "1"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stdout[-3000:] + "\n" + p.stderr[-6000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -96,7 +97,7 @@ def test_driver_scale_command_eight_ranks_on_one_gpu():
     port = 23100 + os.getpid() % 500
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1",
-           "--batch", "2", "--no-native-leg", "--cfg5-batch", "2", "--cfg5-steps", "1", "--cfg5-warmup", "1"]
+           "--batch", "2", "--full", "--no-native-leg", "--cfg5-batch", "2", "--cfg5-steps", "1", "--cfg5-warmup", "1"]
     p = _run_oversubscribed(cmd, env, 1100)
     assert p.returncode == 0, p.stdout[-3000:] + "\n" + p.stderr[-6000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

@@ -58,3 +58,52 @@ def test_two_piece_weights_are_exact_sums_of_two_bf16_pieces():
     # ties go to even: 1 + 2^-16 (exactly between 1 and 1 + 2^-15) -> 1; 1 + 3 * 2^-16 -> 1 + 2^-14
     t = _round16_(torch.tensor([1.0 + 2.0 ** -16, 1.0 + 3 * 2.0 ** -16]))
     assert t[0].item() == 1.0 and t[1].item() == 1.0 + 2.0 ** -14
+
+
+def test_dump_outputs_writes_the_step_results_at_fixed_positions(tmp_path, monkeypatch):
+    """--dump-outputs: loss, sampled parameters and gradients, whole float buffers, all float32; the sampled positions are the
+    same from call to call, so two runs of the same arguments can be compared element for element."""
+    import bench
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 300)
+    torch.manual_seed(0)
+    m = torch.nn.Sequential(torch.nn.Linear(20, 30), torch.nn.BatchNorm1d(30), torch.nn.Linear(30, 5))
+    loss = m(torch.randn(8, 20)).square().mean()
+    loss.backward()
+    with torch.no_grad():                                     # each parameter's value = its position in the concatenation
+        start = 0
+        for p in m.parameters():
+            p.copy_(torch.arange(start, start + p.numel(), dtype=torch.float32).reshape(p.shape))
+            start += p.numel()
+    want_g = torch.cat([p.grad.reshape(-1) for p in m.parameters()]).numpy()
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), loss.detach(), m)
+    got = {d: {n: np.load(tmp_path / d / (n + ".npy")) for n in ("loss", "params", "grads", "buffers")} for d in ("a", "b")}
+    assert sorted(os.listdir(tmp_path / "a")) == ["buffers.npy", "grads.npy", "loss.npy", "params.npy"]
+    a = got["a"]
+    assert all(v.dtype == np.float32 for v in a.values())
+    assert a["loss"].shape == (1,) and a["loss"][0] == np.float32(loss.item())
+    assert 0 < a["params"].size <= 300 < start and a["params"].shape == a["grads"].shape
+    # distinct positions of the concatenation in increasing order, the same ones for parameters and gradients
+    pos = a["params"].astype(np.int64)
+    assert (np.diff(pos) > 0).all() and pos[0] >= 0 and pos[-1] < start and np.array_equal(want_g[pos], a["grads"])
+    assert a["buffers"].size == 30 + 30                       # running mean and variance; the int64 counter is left out
+    for n in a:
+        assert np.array_equal(a[n], got["b"][n])
+
+
+def test_bench_tune_table_is_committed_and_well_formed():
+    """bench.py pins the conv launch configurations from bench_tune.json: every entry is keyed like ops.ConvPlan's benchmark
+    cache (18 geometry integers, the key-scheme tag, the arithmetic) and holds the three configurations of fwd / dgrad / wgrad;
+    the headline's split-operand arithmetic is covered."""
+    import json
+
+    import bench
+    with open(bench.TUNE_TABLE) as f:
+        table = json.load(f)
+    assert table
+    for key, cfgs in table.items():
+        parts = key.split(",")
+        assert len(parts) == 20 and all(p.lstrip("-").isdigit() for p in parts[:18]) and parts[18] == "k3", key
+        assert parts[19] in ("x3", "native"), key
+        assert len(cfgs) == 3 and all(isinstance(c, int) and c >= 0 for c in cfgs), (key, cfgs)
+    assert any(k.endswith(",x3") and k.startswith("16,") for k in table)

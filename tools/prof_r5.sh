@@ -9,8 +9,8 @@ if [ "$2" != "step-only" ]; then
   # the launch configurations are timed once outside the trace (benchmark mode = cudnn.benchmark, main.py:187) and read back
   # from SELAVI_TUNE_CACHE, so the trace holds the steps themselves and not the tuner's isolated launches
   export SELAVI_TUNE_CACHE=/tmp/selavi_tune_r5.json
-  python bench.py --steps 2 --warmup 1 --no-cpu-baseline --cfg5-steps 1 --cfg5-warmup 1 > /dev/null 2>&1
-  rocprofv3 --kernel-trace --stats -d $out/bench -- python bench.py --steps 10 --warmup 3 --no-cpu-baseline --cfg5-steps 4 --cfg5-warmup 2 > $out/bench_under_rocprof.json 2> $out/bench.err
+  python bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --cfg5-steps 1 --cfg5-warmup 1 > /dev/null 2>&1
+  rocprofv3 --kernel-trace --stats -d $out/bench -- python bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --cfg5-steps 4 --cfg5-warmup 2 > $out/bench_under_rocprof.json 2> $out/bench.err
   python tools/rocprof_summary.py $out/bench 100000 > $out/bench_kernel_summary.txt
   rm -rf $out/bench
 fi
