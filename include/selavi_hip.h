@@ -489,6 +489,31 @@ int slv_logfbank(const void* wav_i16, const int64_t* start_i64, const double* vo
                  int slen, int frame_len, int frame_step, int nfft, int nfilt, const double* twiddle_f64,
                  const int32_t* bins_i32, double preemph, int z_normalize, float* out_f32, slv_stream_t stream);
 
+/* ---------------------------------------------------------------- video retrieval (csrc/retrieval.hip) ----------------
+ * The kNN evaluation of video_retrieval.py / src/retrieval_utils.py:
+ * slv_pool222_f32 / _cl16 replace MaxPool3d / AvgPool3d((2,2,2), stride 2) + Flatten behind layer4 (:86-98): kernel 2,
+ *   stride 2, floor mode, no padding; out [N][C*To*Ho*Wo] fp32 in the view(N, -1) order of an N,C,T,H,W tensor.  avg = 0:
+ *   max (NaN propagates, torch's order), 1: mean of the 8 values.  _cl16 reads bf16 channels-last [N][T][H][W][Cp].
+ *   T, H, W >= 2 (a pooled extent of 0 is an error).
+ * slv_row_sqnorm: out[r] = sum_d x[r][d]^2 (fp32).
+ * slv_segment_mean replaces the averaging of average_features (:290-330): segment s is rows perm[offsets[s]] ..
+ *   perm[offsets[s+1]-1], summed in that order in fp32 and divided by the count; normalize = 1 first divides each row by
+ *   sqrt(sum v^2) (ws: rows floats of workspace, nullable when normalize = 0).  out [n_seg][D]; out_sqnorm (nullable)
+ *   [n_seg] = slv_row_sqnorm of out.
+ * slv_knn_select replaces NearestNeighbors.kneighbors (:410-440) after slv_gemm_nt(queries, bank) made
+ *   dots[rows][ldd]: d^2 = max(q_sqnorm[r] + t_sqnorm[j] - 2 dots[r][j], 0), the k smallest per row (1 <= k <= 64, k <= N)
+ *   written ascending, ties to the lower bank index: d2_out / idx_out [rows][k].
+ */
+int slv_pool222_f32(const float* x, float* out, int64_t N, int C, int T, int H, int W, int avg, slv_stream_t stream);
+int slv_pool222_cl16(const void* x_bf16, float* out, int64_t N, int T, int H, int W, int C, int Cp, int avg,
+                     slv_stream_t stream);
+int slv_row_sqnorm(const float* x, int64_t rows, int D, float* out, slv_stream_t stream);
+int slv_segment_mean(const float* x, int64_t rows, int D, const int32_t* perm, const int32_t* offsets, int64_t n_seg,
+                     int normalize, float* ws /* nullable */, float* out, float* out_sqnorm /* nullable */,
+                     slv_stream_t stream);
+int slv_knn_select(const float* dots, int64_t ldd, int64_t rows, int N, const float* q_sqnorm, const float* t_sqnorm, int k,
+                   float* d2_out, int32_t* idx_out, slv_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

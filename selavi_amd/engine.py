@@ -314,13 +314,23 @@ def _video_blocks(layer):
         yield chain, ds
 
 
-def video_stage_forward(ctx, base, stage, x, aux=None):
+def _layer4_pool(ctx, base, u, layer4_pool):
+    """layer4's output pooled by MaxPool3d / AvgPool3d((2, 2, 2), stride 2) and flattened (the retrieval encoder,
+    reference src/retrieval_utils.py:86-98) instead of the global average pool."""
+    if ctx.training:
+        raise ValueError("layer4_pool is an eval-mode tap (no backward)")
+    return _ops32.pool222(u, layer4_pool, channels=base.layer4[-1].conv2[0][3].out_channels)
+
+
+def video_stage_forward(ctx, base, stage, x, aux=None, layer4_pool=None):
     """One stage of R(2+1)D-18 (torchvision VideoResNet): the stem, or a residual layer
     (layer4 ends with the global average pool -> feat [B,512]).  Returns (output, saved record).
     The trunk is cut into stages so that every stage is its own autograd node: under DDP the
     gradients of layer4 (75 % of the parameters) are all-reduced while layers 3..1 still run backward.
     ``aux``: what the previous stage returned beside its output -- the stem's scale / shift when its output is handed over
-    un-materialised (LAZY_STEM_TAIL: the stem then returns (raw tensor, scale_shift) and layer1 takes that pair)."""
+    un-materialised (LAZY_STEM_TAIL: the stem then returns (raw tensor, scale_shift) and layer1 takes that pair).
+    ``layer4_pool`` ("max" | "avg", eval mode only): layer4 returns its output pooled 2x2x2 and flattened instead of the
+    global average (_layer4_pool); None (default) changes nothing."""
     if ctx.folded is not None and not ctx.training:
         if stage == "stem":
             st = base.stem
@@ -328,6 +338,8 @@ def video_stage_forward(ctx, base, stage, x, aux=None):
         u = x
         for chain, ds in _video_blocks(getattr(base, stage)):
             u = block_fwd_folded(ctx, u, chain, ds)
+        if stage == "layer4" and layer4_pool is not None:
+            return _layer4_pool(ctx, base, u, layer4_pool), None
         return (ctx.ops.avgpool_fwd(u) if stage == "layer4" else u), None
     if stage == "stem":
         st = base.stem
@@ -348,6 +360,8 @@ def video_stage_forward(ctx, base, stage, x, aux=None):
         rec = block_fwd(ctx, u, chain, ds)
         recs.append(rec)
         u = rec.v
+    if stage == "layer4" and layer4_pool is not None:
+        return _layer4_pool(ctx, base, u, layer4_pool), (recs, None)
     if stage == "layer4":
         return ctx.ops.avgpool_fwd(u), (recs, u)
     return u, (recs, None)
@@ -371,11 +385,12 @@ def video_stage_backward(ctx, stage, saved, dout):
     return dv
 
 
-def video_forward(ctx, base, x):
-    """Whole trunk in one call (used by tools/tests): returns (feat [B,512], saved records)."""
+def video_forward(ctx, base, x, layer4_pool=None):
+    """Whole trunk in one call (used by tools/tests): returns (feat [B,512], saved records).
+    layer4_pool: see video_stage_forward (feat is then [B, 512*To*Ho*Wo])."""
     saved, aux = [], None
     for st in VIDEO_STAGES:
-        x, sv = video_stage_forward(ctx, base, st, x, aux)
+        x, sv = video_stage_forward(ctx, base, st, x, aux, layer4_pool=layer4_pool)
         x, aux = x if isinstance(x, tuple) else (x, None)
         saved.append(sv)
     return x, saved

@@ -70,7 +70,9 @@ class Engine:
         return out
 
     @torch.no_grad()
-    def video_features(self, video):
+    def video_features(self, video, layer4_pool=None):
+        """fp32 [B, 512]; layer4_pool "max" | "avg": layer4's output pooled 2x2x2 and flattened instead (the retrieval
+        encoder, reference src/retrieval_utils.py:86-98): [B, 512*To*Ho*Wo]."""
         x = self.v_stem[1](self.v_stem[0](video))               # the stem's first conv converts the fp32 clip itself
         for chain, ds in self.v_blocks:
             y = x
@@ -78,6 +80,8 @@ class Engine:
                 y = l(y)
             shortcut = x if ds is None else ds(x, relu=False)
             x = chain[-1](y, res=shortcut, relu=True)          # relu(bn2(conv) + shortcut)
+        if layer4_pool is not None:
+            return ops.pool222(x, layer4_pool, channels=512)
         return self._pool(x, 512)
 
     @torch.no_grad()

@@ -673,3 +673,104 @@ def sgd_step(params, grads, bufs, lr, momentum, wd, first):
     sizes = (ctypes.c_int64 * n)(*[p.numel() for p in params])
     C.slv_sgd_step(pa.p, ga.p, ba.p, ctypes.addressof(sizes), n, float(lr), float(momentum), float(wd), int(first),
                    stream())
+
+
+# ---------------------------------------------------------------------------------- video retrieval (csrc/retrieval.hip)
+def pool222(x, op="max", channels=None):
+    """MaxPool3d / AvgPool3d((2, 2, 2), stride 2) + Flatten (reference src/retrieval_utils.py:86-98) -> fp32 [N, C*To*Ho*Wo]
+    in the view(N, -1) order of an N,C,T,H,W tensor.  x: fp32 N,C,T,H,W, or bf16 channels-last [N,T,H,W,Cp] whose first
+    ``channels`` channels are real (the 16-bit engine's layout)."""
+    if op not in ("max", "avg"):
+        raise ValueError(f"pool op {op!r}: max | avg")
+    if x.dim() != 5:
+        raise ValueError(f"pool222 takes a 5-D tensor, got {tuple(x.shape)}")
+    x = x.contiguous()
+    if x.dtype == torch.bfloat16:
+        N, T, H, W, Cp = x.shape
+        Cc = channels if channels is not None else Cp
+    elif x.dtype == torch.float32:
+        N, Cc, T, H, W = x.shape
+    else:
+        raise ValueError(f"pool222 takes fp32 N,C,T,H,W or bf16 channels-last, got {x.dtype}")
+    To, Ho, Wo = T // 2, H // 2, W // 2
+    if min(To, Ho, Wo) == 0:
+        raise ValueError(f"pool222: input T,H,W = {T},{H},{W} gives a pooled extent of 0")
+    out = _f32(N, Cc * To * Ho * Wo, device=x.device)
+    if x.dtype == torch.bfloat16:
+        C.slv_pool222_cl16(ptr(x), ptr(out), N, T, H, W, Cc, Cp, int(op == "avg"), stream())
+    else:
+        C.slv_pool222_f32(ptr(x), ptr(out), N, Cc, T, H, W, int(op == "avg"), stream())
+    return out
+
+
+def row_sqnorm(x):
+    """fp32 [R, D] -> [R] sums of squares."""
+    x = x.contiguous()
+    out = _f32(x.shape[0], device=x.device)
+    C.slv_row_sqnorm(ptr(x), x.shape[0], x.shape[1], ptr(out), stream())
+    return out
+
+
+def segment_mean(x, vid_indices, normalize=True):
+    """The averaging of average_features (reference src/retrieval_utils.py:290-330) on the device.
+
+    x: fp32 [R, D] clip features; vid_indices: [R] video ids.  Videos come in the order of their first appearance (the
+    reference's dict insertion order); each video's rows are summed in clip order (optionally each divided by its L2 norm
+    first) and divided by their count.  -> (mean [V, D], video ids [V] int64, first row of each video [V] int64,
+    squared norms of the means [V])."""
+    x = x.contiguous()
+    R, D = x.shape
+    vid = vid_indices.to(device=x.device, dtype=torch.int64)
+    if vid.shape != (R,):
+        raise ValueError(f"segment_mean: {R} rows but video indices of shape {tuple(vid.shape)}")
+    uniq, inv = torch.unique(vid, return_inverse=True)
+    V = uniq.shape[0]
+    rows = torch.arange(R, device=x.device)
+    first = torch.full((V,), R, dtype=torch.int64, device=x.device).scatter_reduce_(0, inv, rows, reduce="amin")
+    order = torch.argsort(first)                          # videos by first appearance
+    rank = torch.empty_like(order)
+    rank[order] = torch.arange(V, device=x.device)
+    seg = rank[inv]
+    perm = torch.sort(seg, stable=True).indices.to(torch.int32)     # rows of each video, in clip order
+    offsets = torch.zeros(V + 1, dtype=torch.int32, device=x.device)
+    offsets[1:] = torch.cumsum(torch.bincount(seg, minlength=V), 0).to(torch.int32)
+    out = _f32(V, D, device=x.device)
+    sq = _f32(V, device=x.device)
+    ws = _f32(R, device=x.device) if normalize else None
+    C.slv_segment_mean(ptr(x), R, D, ptr(perm), ptr(offsets), V, int(bool(normalize)), ptr(ws), ptr(out), ptr(sq), stream())
+    return out, uniq[order], first[order], sq
+
+
+KNN_MAX_K = 64
+# cap of the [chunk, N_bank] fp32 dot-product buffer of knn (the query rows run in chunks under it)
+KNN_CHUNK_BYTES = int(os.environ.get("SELAVI_KNN_CHUNK_BYTES", str(256 << 20)))
+
+
+def knn(queries, bank, k, q_sqnorm=None, bank_sqnorm=None, max_chunk_bytes=None):
+    """Brute-force Euclidean k nearest neighbours (NearestNeighbors(k).kneighbors, reference src/retrieval_utils.py:410-440).
+
+    queries fp32 [Q, D], bank fp32 [N, D] -> (d2 fp32 [Q, k], idx int32 [Q, k]): squared distances ascending, ties to the
+    lower bank index.  The dot products come from slv_gemm_nt in query chunks whose [chunk, N] buffer stays under
+    ``max_chunk_bytes``; slv_knn_select completes d^2 = |q|^2 + |t|^2 - 2 q.t (clamped at 0) and selects."""
+    queries, bank = queries.contiguous(), bank.contiguous()
+    Q, D = queries.shape
+    N = bank.shape[0]
+    if bank.shape[1] != D:
+        raise ValueError(f"knn: queries of dimension {D}, bank of dimension {bank.shape[1]}")
+    if not 1 <= k <= KNN_MAX_K:
+        raise ValueError(f"knn: k = {k} must be in [1, {KNN_MAX_K}]")
+    if k > N:
+        raise ValueError(f"knn: Expected n_neighbors <= n_samples, but n_samples = {N}, n_neighbors = {k}")
+    qs = row_sqnorm(queries) if q_sqnorm is None else q_sqnorm.contiguous()
+    ts = row_sqnorm(bank) if bank_sqnorm is None else bank_sqnorm.contiguous()
+    cap = KNN_CHUNK_BYTES if max_chunk_bytes is None else int(max_chunk_bytes)
+    chunk = max(1, min(Q, cap // (4 * N)))
+    dots = _f32(chunk, N, device=queries.device)
+    d2 = _f32(Q, k, device=queries.device)
+    idx = torch.empty(Q, k, dtype=torch.int32, device=queries.device)
+    for r0 in range(0, Q, chunk):
+        m = min(chunk, Q - r0)
+        C.slv_gemm_nt(ptr(queries[r0:r0 + m]), ptr(bank), 0, ptr(dots), m, N, D, N, stream())
+        C.slv_knn_select(ptr(dots), N, m, N, ptr(qs[r0:r0 + m]), ptr(ts), k, ptr(d2[r0:r0 + m]), ptr(idx[r0:r0 + m]),
+                         stream())
+    return d2, idx

@@ -37,3 +37,16 @@ def warmup_batchnorm(args, model, dataloader, batches=20, group=None):
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             dist.barrier(group=group) if group is not None else dist.barrier()
     return time.time() - start
+
+
+def load_model_parameters(model, model_weights):
+    """utils.py:264-274: copy a state dict into ``model`` by name -- a ``module.`` (DataParallel / DDP) prefix is dropped,
+    names the model does not have are reported and skipped."""
+    self_state = model.state_dict()
+    for name, param in model_weights.items():
+        if 'module.' in name:
+            name = name.replace('module.', '')
+        if name in self_state.keys():
+            self_state[name].copy_(param)
+        else:
+            print("didnt load ", name)
