@@ -514,6 +514,46 @@ int slv_segment_mean(const float* x, int64_t rows, int D, const int32_t* perm, c
 int slv_knn_select(const float* dots, int64_t ldd, int64_t rows, int N, const float* q_sqnorm, const float* t_sqnorm, int k,
                    float* d2_out, int32_t* idx_out, slv_stream_t stream);
 
+/* ---------------------------------------------------------------- fine-tuning (csrc/finetune.hip) ---------------------
+ * The classifier head of finetune_video.py's Finetune_Model (:83-92) with nn.CrossEntropyLoss and utils.accuracy fused
+ * in, its backward, the top-k rank count and the per-tensor-hyperparameter optimizer steps (:150-173, :259-271).
+ * slv_ft_head_fwd: x [B][512] trunk features, W [K][512], bias [K]; l2: u = x / max(||x||, 1e-12); bn: BatchNorm1d(512)
+ *   (train: batch mean, biased variance to normalise, unbiased into running_var with `momentum`; B > 1; eval: running
+ *   statistics); drop (train only): keep mask `mask` [B][512] (nullable: Philox4x32-10 on (seed, offset), element
+ *   b*512+c, keep iff word >= p*2^32, as slv_dropout_masks), scale 1/(1-p); then logits [B][K] = W y + bias.
+ *   Saved for the backward: u [B][512], norms [B] (1 without l2), mean_invstd [2][512] (written whenever bn).
+ *   target (nullable) int64 [B]: dlogits (nullable) = (softmax - onehot) / B, loss [1] = mean cross-entropy,
+ *   correct [2] = correct@1 / correct@5 counts under the rank rule of slv_topk_correct; ws: 3*B floats.
+ *   B <= 64: one launch (one workgroup, rows resident in LDS); B > 64: up to three.
+ * slv_ft_head_bwd: dz = dlogits_in (nullable) + *gout * dlogits_saved (nullable); dW = dz^T y, db = sum_b dz, then through
+ *   the mask, BatchNorm (dgamma / dbeta = column sums of dv * xhat / dv) and the L2 normalisation -> dfeat [B][512].
+ *   ws: 2*B*512 floats, nullable when B <= 64 (one launch; B > 64: three).
+ * slv_topk_correct: correct [2] = #rows whose target t ranks below 1 / 5, rank = #{j: z_j > z_t} + #{j < t: z_j == z_t}
+ *   (ties to the lower class index; a target outside [0, K) is wrong).  One launch, deterministic.
+ * slv_sgd_step_grouped: slv_sgd_step's arithmetic with lr / weight decay / momentum / first-step flag per tensor (HOST
+ *   arrays), 48 tensors per launch.
+ * slv_adam_step: torch.optim.Adam (L2 weight decay added to the gradient, no amsgrad) with per-tensor step_size =
+ *   lr / (1 - beta1^step), bias_correction2_sqrt = sqrt(1 - beta2^step) and weight decay (HOST arrays), 48 per launch.
+ */
+int slv_ft_head_fwd(const float* x, const float* W, const float* bias, const float* gamma, const float* beta,
+                    float* running_mean, float* running_var, const float* mask, uint64_t seed, uint64_t offset,
+                    float p, const int64_t* target, float* logits, float* u, float* norms, float* mean_invstd,
+                    float* dlogits, float* ws, float* loss, float* correct, int B, int K, int l2, int bn, int train,
+                    int drop, float momentum, float eps, slv_stream_t stream);
+int slv_ft_head_bwd(const float* dlogits_in, const float* dlogits_saved, const float* gout, const float* u,
+                    const float* norms, const float* mean_invstd, const float* W, const float* gamma, const float* beta,
+                    const float* mask, uint64_t seed, uint64_t offset, float p, float* dW, float* db, float* dgamma,
+                    float* dbeta, float* dfeat, float* ws, int B, int K, int l2, int bn, int train, int drop,
+                    slv_stream_t stream);
+int slv_topk_correct(const float* scores, int64_t N, int K, const int64_t* target, float* correct, slv_stream_t stream);
+int slv_sgd_step_grouped(const void* const* params, const void* const* grads, const void* const* bufs,
+                         const int64_t* sizes, const float* lrs, const float* weight_decays, const float* momenta,
+                         const int32_t* first_step, int n_tensors, slv_stream_t stream);
+int slv_adam_step(const void* const* params, const void* const* grads, const void* const* exp_avgs,
+                  const void* const* exp_avg_sqs, const int64_t* sizes, const float* step_sizes,
+                  const float* bias_correction2_sqrt, const float* weight_decays, int n_tensors, float beta1,
+                  float beta2, float eps, slv_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,6 +7,7 @@
 // These layers are < 0.1 % of the step's FLOPs and are weight-bandwidth bound: one wave per output
 // column (lanes stride the 512-long reduction), wave butterflies, no LDS tiling needed.
 #include "common.hpp"
+#include "philox.hpp"
 #include "../../include/selavi_hip.h"
 
 namespace slv {
@@ -142,19 +143,7 @@ __global__ __launch_bounds__(256) void heads_ce_total_kernel(const float* __rest
 // Dropout keep-masks (model.py:79,85: Dropout(0.3) before each Linear of MLPv2) from Philox4x32-10 (Salmon et al.,
 // SC'11): element e of the concatenation m1 | m2 is word e % 4 of the block with counter (e / 4, offset) under key
 // seed; keep iff word >= p * 2^32.  A mask is a pure function of (seed, offset, e): no generator state on the device.
-__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1,
-                                              unsigned out[4]) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-    const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-    const unsigned n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
-    c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
+// (philox4x32_10: csrc/philox.hpp)
 // state != nullptr: (seed, offset) are read from device memory -- the form a HIP graph can replay with fresh masks (kernel
 // arguments are frozen at capture; dropout_state_advance_kernel, captured behind this launch, bumps the offset)
 __global__ __launch_bounds__(256) void dropout_masks_kernel(unsigned long long seed, unsigned long long offset,

@@ -708,3 +708,43 @@ class GroupedCE(torch.autograd.Function):
     def backward(fctx, gout):
         (dl,) = fctx.saved_tensors
         return dl * gout, None
+
+
+# ------------------------------------------------------------------------------------------ fine-tune classifier head
+class ClassifierSpec:
+    def __init__(self, bn, l2, p, training, mask=None):
+        self.bn, self.l2, self.p, self.training, self.mask = bn, l2, p, training, mask
+
+
+class ClassifierHeadFunction(torch.autograd.Function):
+    """Finetune_Model's head (reference finetune_video.py:83-92: [L2 norm] -> [BatchNorm1d] -> [Dropout] -> Linear) with
+    nn.CrossEntropyLoss and utils.accuracy fused in: one node over csrc/finetune.hip (ops.ft_head_fwd / ft_head_bwd).
+
+    Inputs: spec, feat [B, 512], target (int64 [B] or None), W, bias, gamma, beta (None without BatchNorm).
+    Outputs: logits [B, K] without a target; (logits, loss [], correct [2] counts) with one.  The backward takes the
+    gradient of the logits, of the loss, or both."""
+
+    @staticmethod
+    def forward(fctx, spec, feat, target, W, bias, gamma, beta):
+        fctx.set_materialize_grads(False)
+        has_t = target is not None
+        logits, loss, correct, saved = ops.ft_head_fwd(
+            feat, W, bias, bn_mod=spec.bn, l2=spec.l2, train=spec.training, p=spec.p, mask=spec.mask,
+            dropout_stream=_dropout_stream, target=target, need_dlogits=has_t and any(fctx.needs_input_grad))
+        if spec.bn is not None and spec.training:
+            spec.bn.note_batch()
+        fctx.saved, fctx.bn, fctx.W, fctx.has_t = saved, spec.bn, W, has_t
+        if not has_t:
+            return logits
+        fctx.mark_non_differentiable(correct)
+        return logits, loss, correct
+
+    @staticmethod
+    def backward(fctx, *grads):
+        dlogits = grads[0]
+        dloss = grads[1] if fctx.has_t else None
+        if dlogits is None and dloss is None:
+            return (None,) * 7
+        dfeat, dW, db, dga, dbe = ops.ft_head_bwd(fctx.saved, fctx.W, fctx.bn, dlogits=dlogits, gout=dloss)
+        fctx.saved = None
+        return None, (dfeat if fctx.needs_input_grad[1] else None), None, dW, db, dga, dbe

@@ -774,3 +774,116 @@ def knn(queries, bank, k, q_sqnorm=None, bank_sqnorm=None, max_chunk_bytes=None)
         C.slv_knn_select(ptr(dots), N, m, N, ptr(qs[r0:r0 + m]), ptr(ts), k, ptr(d2[r0:r0 + m]), ptr(idx[r0:r0 + m]),
                          stream())
     return d2, idx
+
+
+# ---------------------------------------------------------------------------------- fine-tuning (csrc/finetune.hip)
+class FtHeadSaved:
+    """What ft_head_fwd keeps for ft_head_bwd: the rows after the L2 normalisation, their norms, the BatchNorm mean /
+    invstd, the dropout draw (mask tensor or Philox (seed, offset)) and the forward's dlogits."""
+    __slots__ = ("u", "norms", "mi", "mask", "seed", "offset", "p", "drop", "dlogits", "l2", "bn", "train")
+
+
+def ft_head_fwd(x, W, bias, bn_mod=None, l2=False, train=False, p=0.0, mask=None, dropout_stream=None, target=None,
+                need_dlogits=False):
+    """Finetune_Model's head (reference finetune_video.py:83-92) in one launch at B <= 64: [L2 norm] -> [BatchNorm1d]
+    -> [dropout, train only] -> Linear, with the cross-entropy / accuracy epilogue when ``target`` is given.
+
+    bn_mod: the BatchNorm holder (weight, bias, running_mean, running_var, momentum, eps) or None; mask: injected keep
+    mask [B, 512] (else Philox on ``dropout_stream()``'s (seed, offset)).  -> (logits [B, K], loss [] or None,
+    correct [2] (correct@1, correct@5 counts) or None, FtHeadSaved)."""
+    x = x.contiguous()
+    B, D = x.shape
+    K = W.shape[0]
+    if D != 512 or W.shape[1] != 512:
+        raise ValueError(f"ft_head_fwd: the head takes 512-d features, got x {tuple(x.shape)}, W {tuple(W.shape)}")
+    dev = x.device
+    drop = bool(train and p > 0)
+    s = FtHeadSaved()
+    s.l2, s.bn, s.train, s.drop, s.p = bool(l2), bn_mod is not None, bool(train), drop, float(p)
+    s.mask, s.seed, s.offset = None, 0, 0
+    if drop:
+        if mask is not None:
+            s.mask = mask.to(device=dev, dtype=torch.float32).contiguous()
+            if s.mask.shape != (B, 512):
+                raise ValueError(f"dropout mask of shape {tuple(s.mask.shape)}, expected {(B, 512)}")
+        else:
+            s.seed, s.offset = dropout_stream()
+    logits = _f32(B, K, device=dev)
+    s.u, s.norms, s.mi = _f32(B, 512, device=dev), _f32(B, device=dev), _f32(2, 512, device=dev)
+    loss = correct = ws = None
+    s.dlogits = None
+    tg = None
+    if target is not None:
+        tg = target.to(device=dev, dtype=torch.int64).contiguous()
+        if tg.shape != (B,):
+            raise ValueError(f"ft_head_fwd: {B} rows but targets of shape {tuple(tg.shape)}")
+        loss, correct, ws = _f32(1, device=dev), _f32(2, device=dev), _f32(3 * B, device=dev)
+        if need_dlogits:
+            s.dlogits = _f32(B, K, device=dev)
+    bm = bn_mod
+    C.slv_ft_head_fwd(ptr(x), ptr(W), ptr(bias), ptr(bm.weight if bm is not None else None),
+                      ptr(bm.bias if bm is not None else None), ptr(bm.running_mean if bm is not None else None),
+                      ptr(bm.running_var if bm is not None else None), ptr(s.mask), s.seed, s.offset, float(p), ptr(tg),
+                      ptr(logits), ptr(s.u), ptr(s.norms), ptr(s.mi), ptr(s.dlogits), ptr(ws), ptr(loss), ptr(correct),
+                      B, K, int(s.l2), int(s.bn), int(s.train), int(drop),
+                      float(bm.momentum) if bm is not None else 0.1, float(bm.eps) if bm is not None else 1e-5, stream())
+    return logits, (loss.view(()) if loss is not None else None), correct, s
+
+
+def ft_head_bwd(s, W, bn_mod, dlogits=None, gout=None):
+    """Backward of ft_head_fwd: dz = dlogits + gout * (the forward's dlogits).  -> (dfeat [B, 512], dW, db, dgamma,
+    dbeta) (dgamma / dbeta None without BatchNorm)."""
+    B = s.u.shape[0]
+    K = W.shape[0]
+    dev = s.u.device
+    dz = dlogits.contiguous() if dlogits is not None else None
+    dls = s.dlogits if gout is not None else None
+    g = gout.to(dtype=torch.float32).contiguous().reshape(1) if dls is not None else None
+    dW, db, dfeat = _f32(K, 512, device=dev), _f32(K, device=dev), _f32(B, 512, device=dev)
+    dga = dbe = None
+    if s.bn:
+        dga, dbe = _f32(512, device=dev), _f32(512, device=dev)
+    ws = _f32(2 * B * 512, device=dev) if B > 64 else None
+    bm = bn_mod
+    C.slv_ft_head_bwd(ptr(dz), ptr(dls), ptr(g), ptr(s.u), ptr(s.norms), ptr(s.mi), ptr(W),
+                      ptr(bm.weight if s.bn else None), ptr(bm.bias if s.bn else None), ptr(s.mask), s.seed, s.offset,
+                      float(s.p), ptr(dW), ptr(db), ptr(dga), ptr(dbe), ptr(dfeat), ptr(ws), B, K, int(s.l2), int(s.bn),
+                      int(s.train), int(s.drop), stream())
+    return dfeat, dW, db, dga, dbe
+
+
+def topk_correct(scores, target):
+    """[2] float32 device tensor: how many rows of ``scores`` [N, K] have their int64 target in the top 1 / top 5, under
+    the deterministic rule #{j: z_j > z_t} + #{j < t: z_j == z_t} < k (ties go to the lower class index)."""
+    scores = scores.contiguous()
+    if scores.dtype != torch.float32 or scores.dim() != 2:
+        raise ValueError(f"topk_correct takes fp32 [N, K] scores, got {scores.dtype} {tuple(scores.shape)}")
+    N, K = scores.shape
+    tg = target.to(device=scores.device, dtype=torch.int64).contiguous().reshape(-1)
+    if tg.shape[0] != N:
+        raise ValueError(f"topk_correct: {N} rows but {tg.shape[0]} targets")
+    out = _f32(2, device=scores.device)
+    C.slv_topk_correct(ptr(scores), N, K, ptr(tg), ptr(out), stream())
+    return out
+
+
+def sgd_step_grouped(params, grads, bufs, lrs, wds, momenta, firsts):
+    """slv_sgd_step with per-tensor lr / weight decay / momentum / first-step flag (48 tensors per launch)."""
+    n = len(params)
+    pa, ga, ba = PtrArray(params), PtrArray(grads), PtrArray(bufs)
+    sizes = (ctypes.c_int64 * n)(*[p.numel() for p in params])
+    lr_a, wd_a, mu_a = ((ctypes.c_float * n)(*[float(v) for v in vs]) for vs in (lrs, wds, momenta))
+    fi = (ctypes.c_int32 * n)(*[int(bool(v)) for v in firsts])
+    C.slv_sgd_step_grouped(pa.p, ga.p, ba.p, ctypes.addressof(sizes), ctypes.addressof(lr_a), ctypes.addressof(wd_a),
+                           ctypes.addressof(mu_a), ctypes.addressof(fi), n, stream())
+
+
+def adam_step(params, grads, exp_avgs, exp_avg_sqs, step_sizes, bc2_sqrts, wds, beta1, beta2, eps):
+    """torch.optim.Adam's update with per-tensor step size lr / (1 - beta1^step), sqrt(1 - beta2^step) and weight decay
+    (48 tensors per launch)."""
+    n = len(params)
+    pa, ga, ma, va = PtrArray(params), PtrArray(grads), PtrArray(exp_avgs), PtrArray(exp_avg_sqs)
+    sizes = (ctypes.c_int64 * n)(*[p.numel() for p in params])
+    ss, bc, wd = ((ctypes.c_float * n)(*[float(v) for v in vs]) for vs in (step_sizes, bc2_sqrts, wds))
+    C.slv_adam_step(pa.p, ga.p, ma.p, va.p, ctypes.addressof(sizes), ctypes.addressof(ss), ctypes.addressof(bc),
+                    ctypes.addressof(wd), n, float(beta1), float(beta2), float(eps), stream())
