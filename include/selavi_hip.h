@@ -476,6 +476,14 @@ int slv_from_cl16(const void* x_bf16, float* y, int64_t N, int C, int Cp, int64_
  *   T*H*W*3 uint8 frames inside frames_u8, H, W, resized H, resized W, crop y offset, crop x offset, flip}; the
  *   random draws stay on the host (selavi_amd/datasets/video_transforms.py makes them in the reference's order).
  *   out: [B][3][T][S][S] float32.  mean3/std3: host pointers.
+ * slv_clip_augment_color is slv_clip_augment followed by color_jitter (:273-363) and grayscale (:251-270, :498-500) in
+ *   the same launch.  color: B x 12 32-bit words on the device per clip = {stage code x 3 in application order (0 none,
+ *   1 brightness, 2 contrast, 3 saturation; at most one contrast stage), grayscale flag, (float)alpha x 3,
+ *   (float)(1.0 - alpha) x 3, 2 unused}; color_host: the same words on the host (checked there; they also decide whether
+ *   the frame-mean pass is launched).  frame_mean_ws: [B][T] float32 on the device, needed (else nullable) when some
+ *   clip has a contrast stage: a first launch writes the mean gray value of every frame of those clips as they stand in
+ *   front of their contrast stage (float64 sum in a fixed order, rounded once), the second launch writes out.  Every
+ *   product and sum of the stages is rounded separately like torch's on the CPU; two calls give the same bits.
  * slv_logfbank replaces datasets/audio_utils.py:46-72 (python_speech_features.logfbank 0.6 with winfunc = ones,
  *   lowfreq 0, highfreq samplerate/2) for B clips: wav_i16 [B][wav_stride] int16 PCM, start_i64[b] first sample of
  *   the clip's window, volume_f64 nullable per-clip factor (audio_utils.py:42-43), slen samples per window;
@@ -484,6 +492,9 @@ int slv_from_cl16(const void* x_bf16, float* y, int64_t N, int C, int Cp, int64_
  *   frames = slv_logfbank_frames(slen, frame_len, frame_step); z_normalize applies (x - 1.93) / 17.89 (:71-72). */
 int slv_clip_augment(const void* frames_u8, const int64_t* desc, float* out, int B, int T, int S,
                      const float* mean3, const float* std3, slv_stream_t stream);
+int slv_clip_augment_color(const void* frames_u8, const int64_t* desc, const void* color, const void* color_host,
+                           float* frame_mean_ws, float* out, int B, int T, int S, const float* mean3,
+                           const float* std3, slv_stream_t stream);
 int32_t slv_logfbank_frames(int slen, int frame_len, int frame_step);   /* sigproc.framesig frame count; -1 on bad sizes */
 int slv_logfbank(const void* wav_i16, const int64_t* start_i64, const double* volume_f64, int64_t wav_stride, int B,
                  int slen, int frame_len, int frame_step, int nfft, int nfilt, const double* twiddle_f64,

@@ -4,6 +4,9 @@
 //   slv_clip_augment   datasets/video_transforms.py:462-510  uint8 THWC frames -> normalised, short-side-resized
 //                      (bilinear, align_corners=False), cropped, optionally flipped float32 CTHW clip.  One read
 //                      of the source bytes, one write of the clip; the reference materialises four intermediates.
+//   slv_clip_augment_color  the same plus color_jitter (:273-363) and grayscale (:251-270, :498-500): the stage chain
+//                      runs in registers behind the sampling; a contrast stage needs the mean gray value of each frame
+//                      first, which a pass of its own recomputes from the uint8 source (no float clip is read back).
 //   slv_logfbank       datasets/audio_utils.py:46-72 -> python_speech_features.logfbank (0.6): pre-emphasis, framing
 //                      (rectangular window), |rfft|^2/nfft, triangular mel filterbank, log -- in float64 like numpy,
 //                      stored as float32 [B][1][nfilt][frames].
@@ -36,25 +39,14 @@ __device__ __forceinline__ float norm_px(unsigned char v, float mean, float stdv
   return ((float)v / 255.0f - mean) / stdv;      // video_transforms.py:475-478, one rounding per step like torch
 }
 
-// grid (ceil(S*S/256), T, B); thread = one output pixel, all three channels (the source is channel-interleaved)
-__global__ __launch_bounds__(256) void clip_augment_kernel(const unsigned char* __restrict__ src,
-                                                           const ClipDesc* __restrict__ desc, float* __restrict__ out,
-                                                           int T, int S, float m0, float m1, float m2, float s0,
-                                                           float s1, float s2) {
-  const int p = blockIdx.x * 256 + threadIdx.x;
-  if (p >= S * S) return;
-  const int oy = p / S, ox = p - oy * S, t = blockIdx.y, b = blockIdx.z;
-  const ClipDesc d = desc[b];
-  const int H = (int)d.H, W = (int)d.W, nh = (int)d.nh, nw = (int)d.nw;
-  const int ry = oy + (int)d.y_off, rx = (d.flip ? S - 1 - ox : ox) + (int)d.x_off;
-  const unsigned char* f = src + d.src_off + (size_t)t * H * W * 3;
-  const float mean[3] = {m0, m1, m2}, stdv[3] = {s0, s1, s2};
-  float* o = out + (((size_t)b * 3) * T + t) * S * S + p;
-  const size_t cstride = (size_t)T * S * S;
+// one output pixel of frame f (all three channels: the source is channel-interleaved) at row ry / column rx of the
+// resized image -- the spatial sampling every kernel below shares
+__device__ __forceinline__ void sample_px(const unsigned char* __restrict__ f, int H, int W, int nh, int nw, int ry,
+                                          int rx, const float (&mean)[3], const float (&stdv)[3], float (&px)[3]) {
   if (nh == H && nw == W) {                      // random_short_side_scale_jitter returned the images unchanged
     const unsigned char* q = f + ((size_t)ry * W + rx) * 3;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) o[c * cstride] = norm_px(q[c], mean[c], stdv[c]);
+    for (int c = 0; c < 3; ++c) px[c] = norm_px(q[c], mean[c], stdv[c]);
     return;
   }
   int y0, y1, x0, x1;
@@ -68,8 +60,132 @@ __global__ __launch_bounds__(256) void clip_augment_kernel(const unsigned char* 
     const float p00 = norm_px(q00[c], mean[c], stdv[c]), p01 = norm_px(q01[c], mean[c], stdv[c]);
     const float p10 = norm_px(q10[c], mean[c], stdv[c]), p11 = norm_px(q11[c], mean[c], stdv[c]);
     const float top = __fmaf_rn(p00, wx0, p01 * wx1), bot = __fmaf_rn(p10, wx0, p11 * wx1);
-    o[c * cstride] = __fmaf_rn(top, wy0, bot * wy1);
+    px[c] = __fmaf_rn(top, wy0, bot * wy1);
   }
+}
+
+// grid (ceil(S*S/256), T, B); thread = one output pixel, all three channels
+__global__ __launch_bounds__(256) void clip_augment_kernel(const unsigned char* __restrict__ src,
+                                                           const ClipDesc* __restrict__ desc, float* __restrict__ out,
+                                                           int T, int S, float m0, float m1, float m2, float s0,
+                                                           float s1, float s2) {
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  if (p >= S * S) return;
+  const int oy = p / S, ox = p - oy * S, t = blockIdx.y, b = blockIdx.z;
+  const ClipDesc d = desc[b];
+  const int H = (int)d.H, W = (int)d.W;
+  const int ry = oy + (int)d.y_off, rx = (d.flip ? S - 1 - ox : ox) + (int)d.x_off;
+  const unsigned char* f = src + d.src_off + (size_t)t * H * W * 3;
+  const float mean[3] = {m0, m1, m2}, stdv[3] = {s0, s1, s2};
+  float* o = out + (((size_t)b * 3) * T + t) * S * S + p;
+  const size_t cstride = (size_t)T * S * S;
+  float px[3];
+  sample_px(f, H, W, (int)d.nh, (int)d.nw, ry, rx, mean, stdv, px);
+#pragma unroll
+  for (int c = 0; c < 3; ++c) o[c * cstride] = px[c];
+}
+
+// ---- colour jitter / grayscale (video_transforms.py:251-363, :491-500) ------------------------------------------------
+// Every product and every sum below is rounded on its own, in the order torch evaluates them on the T x 3 x S x S float32
+// clip (images * alpha + other * (1 - alpha), the two scalars rounded to float32 on the host): __fmul_rn / __fadd_rn are
+// never contracted into a fused multiply-add.
+enum { CJ_NONE = 0, CJ_BRIGHTNESS = 1, CJ_CONTRAST = 2, CJ_SATURATION = 3 };
+struct ColorDesc {          // one per clip, 12 x 32 bit on the device (and, for the argument checks, on the host)
+  int stage[3];             // CJ_* in application order
+  int gray;                 // grayscale(frames) after the stages (:498-500)
+  float alpha[3];           // (float)alpha of stage i
+  float beta[3];            // (float)(1.0 - alpha) of stage i, formed in float64 on the host
+  int pad[2];
+};
+
+// grayscale (:262-266): the indices as written there (the function assumes BGR), summed left to right
+__device__ __forceinline__ float gray_px(const float (&px)[3]) {
+  return __fadd_rn(__fadd_rn(__fmul_rn(0.299f, px[2]), __fmul_rn(0.587f, px[1])), __fmul_rn(0.114f, px[0]));
+}
+
+// blend (:248) with an image that is the same in its three channels
+__device__ __forceinline__ void blend_px(float (&px)[3], float other, float alpha, float beta) {
+  const float o = __fmul_rn(other, beta);
+#pragma unroll
+  for (int c = 0; c < 3; ++c) px[c] = __fadd_rn(__fmul_rn(px[c], alpha), o);
+}
+
+// stages [0, n) of one clip's chain on one pixel; frame_mean: the gray mean of this frame for the contrast stage
+__device__ __forceinline__ void color_stages(float (&px)[3], const ColorDesc& cd, int n, float frame_mean) {
+  for (int i = 0; i < n; ++i) {
+    const int st = cd.stage[i];
+    if (st == CJ_BRIGHTNESS) blend_px(px, 0.f, cd.alpha[i], cd.beta[i]);
+    else if (st == CJ_CONTRAST) blend_px(px, frame_mean, cd.alpha[i], cd.beta[i]);
+    else if (st == CJ_SATURATION) blend_px(px, gray_px(px), cd.alpha[i], cd.beta[i]);
+  }
+}
+
+// pass 1 -- grid (T, B), GM_THREADS threads: the mean gray value of frame t as clip b stands in front of its contrast
+// stage (:341-342; the mean over three equal channels is the mean over the pixels).  float64, fixed order: thread i sums
+// pixels i, i + GM_THREADS, ... and the partial sums go through a fixed tree, so every launch gives the same bits.
+// 1024 threads: a (clip, frame) is one workgroup, so a batch of 16 x 16 is one workgroup per CU, and the sampling is
+// ALU-bound per pixel (24 IEEE divides) -- four waves per SIMD instead of one to overlap it with the byte loads.
+constexpr int GM_THREADS = 1024;
+__global__ __launch_bounds__(GM_THREADS) void clip_gray_mean_kernel(const unsigned char* __restrict__ src,
+                                                             const ClipDesc* __restrict__ desc,
+                                                             const ColorDesc* __restrict__ color,
+                                                             float* __restrict__ frame_mean, int T, int S, float m0,
+                                                             float m1, float m2, float s0, float s1, float s2) {
+  __shared__ double part[GM_THREADS];
+  const int t = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+  const ColorDesc cd = color[b];
+  int k = -1;
+  for (int i = 0; i < 3; ++i)
+    if (cd.stage[i] == CJ_CONTRAST && k < 0) k = i;
+  if (k < 0) return;                             // block-uniform: no barrier has been reached
+  const ClipDesc d = desc[b];
+  const int H = (int)d.H, W = (int)d.W, nh = (int)d.nh, nw = (int)d.nw;
+  const unsigned char* f = src + d.src_off + (size_t)t * H * W * 3;
+  const float mean[3] = {m0, m1, m2}, stdv[3] = {s0, s1, s2};
+  double acc = 0.0;
+  for (int p = tid; p < S * S; p += GM_THREADS) {
+    const int oy = p / S, ox = p - oy * S;
+    const int ry = oy + (int)d.y_off, rx = (d.flip ? S - 1 - ox : ox) + (int)d.x_off;
+    float px[3];
+    sample_px(f, H, W, nh, nw, ry, rx, mean, stdv, px);
+    color_stages(px, cd, k, 0.f);
+    acc += (double)gray_px(px);
+  }
+  part[tid] = acc;
+  __syncthreads();
+  for (int w = GM_THREADS / 2; w > 0; w >>= 1) {
+    if (tid < w) part[tid] += part[tid + w];
+    __syncthreads();
+  }
+  if (tid == 0) frame_mean[(size_t)b * T + t] = (float)(part[0] / (double)((long long)S * S));
+}
+
+// pass 2 -- grid (ceil(S*S/256), T, B) like clip_augment_kernel: sampling, the whole chain and the grayscale flag in
+// registers, one write of the clip
+__global__ __launch_bounds__(256) void clip_augment_color_kernel(const unsigned char* __restrict__ src,
+                                                                 const ClipDesc* __restrict__ desc,
+                                                                 const ColorDesc* __restrict__ color,
+                                                                 const float* __restrict__ frame_mean,
+                                                                 float* __restrict__ out, int T, int S, float m0,
+                                                                 float m1, float m2, float s0, float s1, float s2) {
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  if (p >= S * S) return;
+  const int oy = p / S, ox = p - oy * S, t = blockIdx.y, b = blockIdx.z;
+  const ClipDesc d = desc[b];
+  const ColorDesc cd = color[b];
+  const int H = (int)d.H, W = (int)d.W;
+  const int ry = oy + (int)d.y_off, rx = (d.flip ? S - 1 - ox : ox) + (int)d.x_off;
+  const unsigned char* f = src + d.src_off + (size_t)t * H * W * 3;
+  const float mean[3] = {m0, m1, m2}, stdv[3] = {s0, s1, s2};
+  float px[3];
+  sample_px(f, H, W, (int)d.nh, (int)d.nw, ry, rx, mean, stdv, px);
+  const bool contrast = cd.stage[0] == CJ_CONTRAST || cd.stage[1] == CJ_CONTRAST || cd.stage[2] == CJ_CONTRAST;
+  color_stages(px, cd, 3, contrast ? frame_mean[(size_t)b * T + t] : 0.f);
+  if (cd.gray) px[0] = px[1] = px[2] = gray_px(px);
+  float* o = out + (((size_t)b * 3) * T + t) * S * S + p;
+  const size_t cstride = (size_t)T * S * S;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) o[c * cstride] = px[c];
 }
 
 // ---- audio --------------------------------------------------------------------------------------------------------
@@ -147,6 +263,38 @@ int slv_clip_augment(const void* frames_u8, const int64_t* desc, float* out, int
   hipLaunchKernelGGL(clip_augment_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const unsigned char*)frames_u8,
                      (const ClipDesc*)desc, (float*)out, T, S, mean3[0], mean3[1], mean3[2], std3[0], std3[1],
                      std3[2]);
+  SLV_LAUNCH_CHECK();
+  return 0;
+}
+
+int slv_clip_augment_color(const void* frames_u8, const int64_t* desc, const void* color, const void* color_host,
+                           float* frame_mean_ws, float* out, int B, int T, int S, const float* mean3,
+                           const float* std3, void* stream) {
+  using namespace slv;
+  SLV_CHECK_ARG(frames_u8 && desc && color && color_host && out && mean3 && std3, "null pointer");
+  SLV_CHECK_ARG(B > 0 && T > 0 && S > 0 && B <= 65535 && T <= 65535, "bad sizes");
+  const ColorDesc* ch = (const ColorDesc*)color_host;
+  bool any_contrast = false;
+  for (int b = 0; b < B; ++b) {
+    int n_contrast = 0;
+    for (int i = 0; i < 3; ++i) {
+      SLV_CHECK_ARG(ch[b].stage[i] >= CJ_NONE && ch[b].stage[i] <= CJ_SATURATION, "unknown stage code");
+      n_contrast += ch[b].stage[i] == CJ_CONTRAST;
+    }
+    SLV_CHECK_ARG(n_contrast <= 1, "more than one contrast stage in a clip");
+    any_contrast = any_contrast || n_contrast;
+  }
+  SLV_CHECK_ARG(!any_contrast || frame_mean_ws, "a contrast stage needs the B x T frame-mean workspace");
+  if (any_contrast) {
+    hipLaunchKernelGGL(clip_gray_mean_kernel, dim3(T, B), dim3(GM_THREADS), 0, (hipStream_t)stream,
+                       (const unsigned char*)frames_u8, (const ClipDesc*)desc, (const ColorDesc*)color, frame_mean_ws, T,
+                       S, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2]);
+    SLV_LAUNCH_CHECK();
+  }
+  dim3 grid(cdiv((long)S * S, 256), T, B);
+  hipLaunchKernelGGL(clip_augment_color_kernel, grid, dim3(256), 0, (hipStream_t)stream,
+                     (const unsigned char*)frames_u8, (const ClipDesc*)desc, (const ColorDesc*)color, frame_mean_ws,
+                     (float*)out, T, S, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2]);
   SLV_LAUNCH_CHECK();
   return 0;
 }

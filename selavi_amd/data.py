@@ -53,3 +53,18 @@ class SyntheticRetrievalDataset(torch.utils.data.Dataset):
         video = (self._pattern(9176 + lab, 1.0) + self._pattern((self.seed * 1000003 + vid) * 7 + 2, 0.5)
                  + 0.5 * torch.randn(3, self.T, self.S, self.S, generator=g))
         return video, lab, clip, vid
+
+
+class SyntheticFramesDataset(SyntheticRetrievalDataset):
+    """The same clips as decoded frames: ``dataset[i] -> (frames[T,H,W,3] uint8, label, clip_idx, vid_idx)``, what a
+    video decoder hands to clip_augmentation (datasets/video_transforms.py).  The float clip is generated at
+    max(H, W) square, cut to H x W, de-normalised with the pipeline's mean / std and rounded to bytes."""
+
+    def __init__(self, H, W, **kw):
+        super().__init__(S=max(H, W), **kw)
+        self.H, self.W = H, W
+
+    def __getitem__(self, i):
+        video, lab, clip, vid = super().__getitem__(i)
+        frames = ((video[:, :, :self.H, :self.W] * 0.225 + 0.45) * 255.0).round().clamp(0, 255).to(torch.uint8)
+        return frames.permute(1, 2, 3, 0).contiguous(), lab, clip, vid

@@ -4,6 +4,10 @@ The reference normalises, permutes, resizes (bilinear), crops and flips one clip
 intermediate tensors.  Here the random draws are made on the host with the SAME np.random calls in the SAME order
 (:52 size, :121-125 crop offsets, :158 flip), and one kernel (csrc/input.hip: slv_clip_augment) reads the uint8
 frames once and writes the float32 C x T x S x S clip -- for a whole batch per launch.
+
+Colour jitter and grayscale (:273-363, :491-500) ride on the same kernel (slv_clip_augment_color): their draws are made
+by sample_color_params, again with the reference's generator calls, and ClipAugmenter is the per-batch callable that
+draws for every clip what the reference's worker would draw for it.
 """
 import math
 
@@ -57,9 +61,63 @@ def sample_spatial_params(height, width, spatial_idx=-1, min_scale=256, max_scal
     return nh, nw, y_off, x_off, flip
 
 
-def clip_augmentation_batch(clips, params, crop_size, out=None):
+BRIGHTNESS, CONTRAST, SATURATION = 1, 2, 3       # stage codes of slv_clip_augment_color (0: none)
+_JITTER = (BRIGHTNESS, CONTRAST, SATURATION)     # color_jitter's list order (:288-294)
+
+
+class ColorParams:
+    """The colour draws of one clip: ``stages`` = ((code, alpha), ...) in application order (empty: the jitter gate
+    said no, or colorjitter is off), ``gray``: grayscale applied after them."""
+    __slots__ = ("stages", "gray")
+
+    def __init__(self, stages=(), gray=False):
+        self.stages, self.gray = tuple((int(c), float(a)) for c, a in stages), bool(gray)
+
+    def __eq__(self, other):
+        return isinstance(other, ColorParams) and (self.stages, self.gray) == (other.stages, other.gray)
+
+    def __repr__(self):
+        return f"ColorParams(stages={self.stages}, gray={self.gray})"
+
+
+def sample_color_params(colorjitter=False, use_grayscale=False, var=0.4):
+    """The host half of the colour part of clip_augmentation (:491-500), called after sample_spatial_params for the
+    same clip: the gate draw, color_jitter's permutation (:297) and one alpha per stage in application order
+    (:320,339,359), then the grayscale gate.  With both flags off it draws nothing."""
+    stages, gray = [], False
+    if colorjitter:
+        if np.random.uniform() >= 0.2:
+            order = np.random.permutation(np.arange(3))
+            for idx in range(3):
+                stages.append((_JITTER[order[idx]], 1.0 + np.random.uniform(-var, var)))
+    if use_grayscale:
+        gray = bool(np.random.uniform() >= 0.8)
+    return ColorParams(stages, gray)
+
+
+def _color_desc(color):
+    """B x 12 32-bit words: stage codes x 3, grayscale flag, float32 alpha x 3, float32 (1 - alpha) x 3, 2 unused.
+    torch multiplies a float32 tensor by a Python float in float32, so alpha and the float64 difference 1 - alpha
+    (blend, :248) are rounded to float32 separately."""
+    words = np.zeros((len(color), 12), dtype=np.int32)
+    fl = words.view(np.float32)
+    for b, cp in enumerate(color):
+        if cp is None:
+            continue
+        if len(cp.stages) > 3:
+            raise ValueError("at most three colour stages per clip")
+        for i, (code, alpha) in enumerate(cp.stages):
+            words[b, i] = code
+            fl[b, 4 + i] = np.float32(alpha)
+            fl[b, 7 + i] = np.float32(1 - alpha)
+        words[b, 3] = int(cp.gray)
+    return words
+
+
+def clip_augmentation_batch(clips, params, crop_size, out=None, color=None):
     """clips: list of uint8 device tensors T x H x W x 3 (same T; H, W may differ per clip), or one B x T x H x W x 3
-    tensor.  params: per clip (resized H, resized W, y offset, x offset, flip).  -> B x 3 x T x S x S float32."""
+    tensor.  params: per clip (resized H, resized W, y offset, x offset, flip).  color: None, or per clip a ColorParams
+    (None for a clip without colour work).  -> B x 3 x T x S x S float32."""
     if torch.is_tensor(clips):
         assert clips.dtype == torch.uint8 and clips.dim() == 5 and clips.shape[-1] == 3 and clips.is_cuda
         B, T, H, W = clips.shape[:4]
@@ -81,19 +139,69 @@ def clip_augmentation_batch(clips, params, crop_size, out=None):
         if not (0 <= yo and yo + crop_size <= nh and 0 <= xo and xo + crop_size <= nw):
             raise ValueError("crop window outside the resized frame")
         desc[b] = (offs[b], H, W, nh, nw, yo, xo, int(flip))
-    desc_d = torch.from_numpy(desc).to(buf.device, non_blocking=False)
+    if color is not None and len(color) != B:
+        raise ValueError("one colour-parameter object (or None) per clip")
+    words = None if color is None else _color_desc(color)
+    # one upload: the spatial descriptors, then (colour path) the colour words behind them
+    host = desc.view(np.uint8).reshape(-1) if words is None else \
+        np.concatenate([desc.view(np.uint8).reshape(-1), words.view(np.uint8).reshape(-1)])
+    dev = torch.from_numpy(host).to(buf.device, non_blocking=False)
     if out is None:
         out = torch.empty((B, 3, T, crop_size, crop_size), dtype=torch.float32, device=buf.device)
     assert out.shape == (B, 3, T, crop_size, crop_size) and out.dtype == torch.float32
-    C.slv_clip_augment(ptr(buf), ptr(desc_d), ptr(out), B, T, crop_size, _MEAN.ctypes.data, _STD.ctypes.data, stream())
+    if words is None:
+        C.slv_clip_augment(ptr(buf), ptr(dev), ptr(out), B, T, crop_size, _MEAN.ctypes.data, _STD.ctypes.data, stream())
+        return out
+    ws = None
+    if (words[:, :3] == CONTRAST).any():
+        ws = torch.empty((B, T), dtype=torch.float32, device=buf.device)
+    C.slv_clip_augment_color(ptr(buf), ptr(dev), ptr(dev) + desc.nbytes, words.ctypes.data, ptr(ws), ptr(out), B, T,
+                             crop_size, _MEAN.ctypes.data, _STD.ctypes.data, stream())
     return out
+
+
+class ClipAugmenter:
+    """clip_augmentation (:462-504) for a batch on the device, with the reference's keyword names.  Called on a
+    B x T x H x W x 3 uint8 device tensor or a list of T x H x W x 3 ones; ``spatial_idx`` in the call (an int or one
+    per clip) overrides the constructor's for the test-time views.  Per clip, in clip order, it draws exactly what the
+    reference's worker draws for that clip: the spatial draws, then the colour draws.  use_gaussian is accepted and
+    unused, like in the reference (no draw, no effect).  -> B x 3 x T x S x S float32."""
+
+    def __init__(self, spatial_idx=-1, min_scale=256, max_scale=320, crop_size=224, colorjitter=False,
+                 use_grayscale=False, use_gaussian=False):
+        self.spatial_idx, self.min_scale, self.max_scale, self.crop_size = spatial_idx, min_scale, max_scale, crop_size
+        self.colorjitter, self.use_grayscale, self.use_gaussian = bool(colorjitter), bool(use_grayscale), use_gaussian
+
+    def sample(self, shapes, spatial_idx=None):
+        """shapes: (H, W) per clip -> (spatial params per clip, ColorParams per clip or None when both flags are off)."""
+        sidx = self.spatial_idx if spatial_idx is None else spatial_idx
+        if isinstance(sidx, (int, np.integer)):
+            sidx = [int(sidx)] * len(shapes)
+        sidx = [int(i) for i in sidx]
+        if len(sidx) != len(shapes):
+            raise ValueError("one spatial_idx per clip")
+        with_color = self.colorjitter or self.use_grayscale
+        params, color = [], []
+        for (H, W), si in zip(shapes, sidx):
+            params.append(sample_spatial_params(H, W, si, self.min_scale, self.max_scale, self.crop_size))
+            if with_color:
+                color.append(sample_color_params(self.colorjitter, self.use_grayscale))
+        return params, (color if with_color else None)
+
+    def __call__(self, clips, spatial_idx=None, out=None):
+        if torch.is_tensor(clips):
+            shapes = [(clips.shape[2], clips.shape[3])] * clips.shape[0]
+        else:
+            shapes = [(c.shape[1], c.shape[2]) for c in clips]
+        params, color = self.sample(shapes, spatial_idx)
+        return clip_augmentation_batch(clips, params, self.crop_size, out=out, color=color)
 
 
 def clip_augmentation(frames, spatial_idx=-1, min_scale=256, max_scale=320, crop_size=224, colorjitter=False,
                       use_grayscale=False, use_gaussian=False):
     """One clip, the reference's signature (:462-471): frames T x H x W x 3 uint8 (device) -> 3 x T x S x S float32."""
     if colorjitter or use_grayscale or use_gaussian:
-        raise NotImplementedError("colour jitter / grayscale / gaussian are off in the reference's defaults "
-                                  "(opt.py:47-52) and are not part of the device pipeline")
+        raise NotImplementedError("the single-clip entry point covers the spatial part only: use ClipAugmenter("
+                                  "..., colorjitter=, use_grayscale=, use_gaussian=) for colour jitter / grayscale")
     prm = sample_spatial_params(frames.shape[1], frames.shape[2], spatial_idx, min_scale, max_scale, crop_size)
     return clip_augmentation_batch([frames], [prm], crop_size)[0]

@@ -7,7 +7,11 @@ Same names, signatures, return values and checkpoint layout as the reference.  T
 accuracy epilogue is one autograd node over csrc/finetune.hip (nn.ClassifierHeadFunction) under the trunk's stage nodes;
 the optimizer steps every per-tensor param group in one fused table (optim.SGD / optim.Adam).  Video decoding is out of
 scope: ``main`` takes dataset objects yielding ``(video, target, _, video_idx)``; ``--dataset synthetic`` builds
-data.SyntheticRetrievalDataset ones.
+data.SyntheticRetrievalDataset ones.  A dataset may hand out the video as augmented float32 ``3 x T x S x S`` clips, or
+as decoded ``T x H x W x 3`` uint8 frames: those go through datasets.video_transforms.ClipAugmenter on the device
+(resize / crop / flip, ``--colorjitter``, ``--test_time_cj``), set up the way the reference sets up AVideoDataset
+(:176-207); a test set then carries the item's spatial-temporal index as the third item (AVideoDataset.py:370-380).
+``--dataset synthetic_uint8`` builds synthetic sets of that kind.
 
 Divergences from the reference (it crashes or wastes work there; nothing observable changes):
   - train / evaluate take what they need as arguments instead of reading a global ``args``;
@@ -32,6 +36,7 @@ from torch import nn
 
 from . import nn as snn
 from . import ops, optim
+from .datasets.video_transforms import ClipAugmenter
 from .model import load_model
 from .utils import AverageMeter, load_model_parameters, save_checkpoint, video_accuracy
 from .warmup_scheduler import GradualWarmupScheduler
@@ -63,7 +68,9 @@ NUM_CLASSES = {
     'hmdb51': 51,
     'ucf101': 101,
     'synthetic': 11,
+    'synthetic_uint8': 11,       # the synthetic sets as uint8 frames larger than the crop
 }
+SYNTHETIC = ('synthetic', 'synthetic_uint8')
 
 
 def get_video_dim(vid_base_arch='r2plus1d_18'):
@@ -130,10 +137,69 @@ class Finetune_Model(nn.Module):
                                                 bn.bias if bn is not None else None)
 
 
+def _crop_size(args):
+    """finetune_video.py:183,198; ``--synthetic_crop`` shrinks it for the synthetic sets."""
+    if args.dataset in SYNTHETIC and getattr(args, 'synthetic_crop', 0):
+        return args.synthetic_crop
+    return 128 if args.augtype == 1 else 224
+
+
+def build_augmenters(args):
+    """The (train, test) ClipAugmenter for datasets that hand out uint8 frames, from the arguments the way the reference
+    builds its two AVideoDataset (finetune_video.py:176-207, AVideoDataset.py:213-217,358-380): training draws scale,
+    crop and flip (spatial_idx -1) with ``--colorjitter``; testing resizes the short side to the crop and takes view
+    ``index % num_spatial_crops`` (given per clip in the call) with ``--test_time_cj``."""
+    crop = _crop_size(args)
+    if crop in (112, 128):
+        scales = (128, 160)
+    elif crop == 224:
+        scales = (256, 320)
+    else:                        # a synthetic size the reference has no rule for: the 128 rule, in proportion
+        scales = (crop, crop * 5 // 4)
+    train_aug = ClipAugmenter(spatial_idx=-1, min_scale=scales[0], max_scale=scales[1], crop_size=crop,
+                              colorjitter=args.colorjitter)
+    test_aug = ClipAugmenter(spatial_idx=1, min_scale=crop, max_scale=crop, crop_size=crop,
+                             colorjitter=args.test_time_cj)
+    return train_aug, test_aug
+
+
+def is_frames(video):
+    """Decoded frames (B x T x H x W x 3 uint8) as opposed to augmented float clips (B x 3 x T x S x S)."""
+    return video.dtype == torch.uint8 and video.dim() == 5 and video.shape[-1] == 3
+
+
+def device_clips(video, augment, spatial_idx=None):
+    """A batch as the loader hands it out -> B x 3 x T x S x S float32 on the device."""
+    if not is_frames(video):
+        return video.cuda(non_blocking=True)
+    if augment is None:
+        raise ValueError("the dataset hands out uint8 frames: train() / evaluate() need augment=ClipAugmenter(...)")
+    return augment(video.cuda(non_blocking=True), spatial_idx=spatial_idx)
+
+
+_noted = set()
+
+
+def _note_colorjitter_without_frames():
+    """Once per process: the flag is not dropped in silence."""
+    if 'colorjitter' not in _noted:
+        _noted.add('colorjitter')
+        logger.info("--colorjitter True has no effect on this training set: it hands out float clips, and colour jitter "
+                    "is part of the device clip augmentation of uint8 frames (see --dataset synthetic_uint8)")
+
+
 def _synthetic_datasets(args):
-    from .data import SyntheticRetrievalDataset
-    S = args.synthetic_crop or (128 if args.augtype == 1 else 224)
+    from .data import SyntheticFramesDataset, SyntheticRetrievalDataset
+    S = _crop_size(args)
     fold = int(args.fold)
+    if args.dataset == 'synthetic_uint8':
+        H, W = S * 5 // 4, S * 3 // 2                  # larger than the crop, landscape
+        train = SyntheticFramesDataset(H, W, n_videos=args.synthetic_videos, clips_per_video=args.train_clips_per_video,
+                                       T=args.clip_len, n_classes=NUM_CLASSES['synthetic'], seed=1000 + fold)
+        test = SyntheticFramesDataset(H, W, n_videos=max(args.synthetic_videos // 2, 1),
+                                      clips_per_video=args.num_spatial_crops * args.val_clips_per_video,
+                                      T=args.clip_len, n_classes=NUM_CLASSES['synthetic'], seed=2000 + fold)
+        return train, test
     train = SyntheticRetrievalDataset(n_videos=args.synthetic_videos, clips_per_video=args.train_clips_per_video,
                                       T=args.clip_len, S=S, n_classes=NUM_CLASSES['synthetic'], seed=1000 + fold)
     test = SyntheticRetrievalDataset(n_videos=max(args.synthetic_videos // 2, 1),
@@ -192,7 +258,7 @@ def main(args, writer=None, dataset=None, dataset_test=None):
     model.feature_extract = bool(args.feature_extract)
 
     if dataset is None or dataset_test is None:
-        if args.dataset != 'synthetic':
+        if args.dataset not in SYNTHETIC:
             raise NotImplementedError("video decoding is out of scope: pass dataset= and dataset_test= "
                                       "(items (video, target, _, video_idx)) or use --dataset synthetic")
         dataset, dataset_test = _synthetic_datasets(args)
@@ -201,6 +267,9 @@ def main(args, writer=None, dataset=None, dataset_test=None):
                                               num_workers=args.workers, pin_memory=True, drop_last=True, shuffle=True)
     data_loader_test = torch.utils.data.DataLoader(dataset_test, batch_size=args.batch_size, sampler=None,
                                                    num_workers=args.workers, pin_memory=True, drop_last=False)
+
+    train_aug, test_aug = build_augmenters(args)
+    nsc = args.num_spatial_crops
 
     optimizer = build_optimizer(args, model)
     lr_scheduler = build_scheduler(args, optimizer)
@@ -216,18 +285,20 @@ def main(args, writer=None, dataset=None, dataset_test=None):
         logger.info(f"Resuming from epoch: {args.start_epoch}")
 
     if args.test_only:
-        _, vid_acc1, vid_acc5 = evaluate(model, data_loader_test, epoch=args.start_epoch, writer=writer, ds=args.dataset)
+        _, vid_acc1, vid_acc5 = evaluate(model, data_loader_test, epoch=args.start_epoch, writer=writer, ds=args.dataset,
+                                         augment=test_aug, num_spatial_crops=nsc)
         return vid_acc1, vid_acc5, args.start_epoch
 
     start_time = time.time()
     best_vid_acc_1, best_vid_acc_5, best_epoch = -1, -1, 0
     for epoch in range(args.start_epoch, args.epochs):
         logger.info(f'Start training epoch: {epoch}')
-        train(model, optimizer, data_loader, epoch, writer=writer, ds=args.dataset)
+        train(model, optimizer, data_loader, epoch, writer=writer, ds=args.dataset, augment=train_aug)
         logger.info(f'Start evaluating epoch: {epoch}')
         if lr_scheduler is not None:
             lr_scheduler.step()
-        _, vid_acc1, vid_acc5 = evaluate(model, data_loader_test, epoch=epoch, writer=writer, ds=args.dataset)
+        _, vid_acc1, vid_acc5 = evaluate(model, data_loader_test, epoch=epoch, writer=writer, ds=args.dataset,
+                                         augment=test_aug, num_spatial_crops=nsc)
         if vid_acc1 > best_vid_acc_1:
             best_vid_acc_1, best_vid_acc_5, best_epoch = vid_acc1, vid_acc5, epoch
         if args.output_dir:
@@ -242,9 +313,10 @@ def _lr_of(optimizer):
     return optimizer.param_groups[0]["lr"]
 
 
-def train(model, optimizer, loader, epoch, writer=None, ds='hmdb51', log_every=50):
+def train(model, optimizer, loader, epoch, writer=None, ds='hmdb51', log_every=50, augment=None):
     """finetune_video.py:277-350 -> (epoch, loss_avg, top1_avg, top5_avg).  The loss and correct counts of every step
-    stay on the device; they are read back at the log lines and at the end of the epoch."""
+    stay on the device; they are read back at the log lines and at the end of the epoch.  ``augment``: the training
+    ClipAugmenter, for loaders that hand out uint8 frames."""
     model.train()
     batch_time, data_time = AverageMeter(), AverageMeter()
     losses, top1, top5 = AverageMeter(), AverageMeter(), AverageMeter()
@@ -266,7 +338,9 @@ def train(model, optimizer, loader, epoch, writer=None, ds='hmdb51', log_every=5
         data_time.update(time.perf_counter() - end)
         iteration = epoch * len(loader) + it
         video, target, _, _ = batch
-        video, target = video.cuda(non_blocking=True), target.cuda(non_blocking=True)
+        if augment is not None and augment.colorjitter and not is_frames(video):
+            _note_colorjitter_without_frames()
+        video, target = device_clips(video, augment), target.cuda(non_blocking=True)
         output, loss, correct = model(video, target)
         model.zero_grad(set_to_none=True)
         if one is None:
@@ -293,10 +367,11 @@ def train(model, optimizer, loader, epoch, writer=None, ds='hmdb51', log_every=5
     return epoch, losses.avg, top1.avg, top5.avg
 
 
-def evaluate(model, val_loader, epoch=0, writer=None, ds='hmdb51'):
+def evaluate(model, val_loader, epoch=0, writer=None, ds='hmdb51', augment=None, num_spatial_crops=3):
     """finetune_video.py:353-436 -> (loss_avg, vid_acc1, vid_acc5).  Logits, targets and video ids of the whole pass
     go into preallocated device buffers; the video-level accuracy is ops.segment_mean + the top-k kernel
-    (utils.video_accuracy), read back once at the end of the pass."""
+    (utils.video_accuracy), read back once at the end of the pass.  ``augment``: the test ClipAugmenter, for loaders that
+    hand out uint8 frames; the view of a clip is its spatial-temporal index (third item) % num_spatial_crops."""
     batch_time, losses, top1 = AverageMeter(), AverageMeter(), AverageMeter()
     model.eval()
     n = len(val_loader.dataset)
@@ -310,8 +385,9 @@ def evaluate(model, val_loader, epoch=0, writer=None, ds='hmdb51'):
     with torch.no_grad():
         end = time.perf_counter()
         for batch_idx, batch in enumerate(val_loader):
-            video, target, _, video_idx = batch
-            video = video.cuda(non_blocking=True)
+            video, target, st_idx, video_idx = batch
+            views = [int(i) % num_spatial_crops for i in st_idx] if is_frames(video) else None
+            video = device_clips(video, augment, spatial_idx=views)
             target = target.cuda(non_blocking=True)
             b = video.size(0)
             output, loss, correct = model(video, target)
@@ -339,7 +415,8 @@ def evaluate(model, val_loader, epoch=0, writer=None, ds='hmdb51'):
 
 def parse_args(argv=None):
     """finetune_video.py:439-620: the reference's flags and defaults, plus ``synthetic`` as a dataset and the size of
-    the synthetic sets (--synthetic_videos, --synthetic_crop)."""
+    the synthetic sets (--synthetic_videos, --synthetic_crop); ``synthetic_uint8`` is the synthetic set handing out
+    uint8 frames larger than the crop, so that the device clip augmentation runs."""
     def str2bool(v):
         v = v.lower()
         if v in ('yes', 'true', 't', '1'):
@@ -354,7 +431,7 @@ def parse_args(argv=None):
     add = parser.add_argument
     # DATA
     add('--dataset', default='ucf101', type=str,
-        choices=['kinetics', 'vggsound', 'kinetics_sound', 'ave', 'ucf101', 'hmdb51', 'synthetic'])
+        choices=['kinetics', 'vggsound', 'kinetics_sound', 'ave', 'ucf101', 'hmdb51', 'synthetic', 'synthetic_uint8'])
     add('--root_dir', type=str, default='/path/to/dataset')
     add('--fold', default='1,2,3', type=str)
     add('--clip_len', default=32, type=int)

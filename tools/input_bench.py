@@ -1,4 +1,5 @@
-"""Throughput of the device input pipeline (slv_clip_augment, slv_logfbank) at the cfg2 batch shape.
+"""Throughput of the device input pipeline (slv_clip_augment, slv_clip_augment_color, slv_logfbank) at the cfg2 batch
+shape.
 
     python tools/input_bench.py            # on the GPU box
 """
@@ -36,6 +37,18 @@ def main():
     byt = src_bytes + out.numel() * 4
     print(f"clip_augment  B={B} T={T} {H}x{W}->{S}: {ms * 1e3:8.1f} us  {B / ms * 1e3:10.0f} clips/s  "
           f"{byt / ms / 1e6:7.1f} GB/s (algorithmic: crop footprint read + clip written)")
+    # the colour path: every clip jittered with contrast last (the longest pass 1: two stages in front of the frame mean),
+    # and grayscale only (pass 2 alone)
+    VT = video_transforms
+    jit = [VT.ColorParams([(VT.SATURATION, 0.8 + 0.02 * b), (VT.BRIGHTNESS, 1.3 - 0.02 * b), (VT.CONTRAST, 0.7 + 0.03 * b)])
+           for b in range(B)]
+    for name, color, reads, what in (("contrast last", jit, 2, "crop footprint read twice + clip written"),
+                                     ("grayscale only", [VT.ColorParams(gray=True)] * B, 1,
+                                      "crop footprint read + clip written")):
+        ms = timeit(lambda: VT.clip_augmentation_batch(clips, prms, S, out=out, color=color))
+        byt = reads * src_bytes + out.numel() * 4
+        print(f"clip_augment_color {name:14s} B={B} T={T} {H}x{W}->{S}: {ms * 1e3:8.1f} us  {B / ms * 1e3:10.0f} clips/s  "
+              f"{byt / ms / 1e6:7.1f} GB/s (algorithmic: {what})")
     wav = (torch.randn(B, 48000 * 2, device="cuda", generator=g) * 3000).to(torch.int16)
     for t in (1, 2):
         ms = timeit(lambda: audio_utils.get_spec_batch(wav, [100] * B, aud_spec_type=t))
