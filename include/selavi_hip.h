@@ -484,6 +484,14 @@ int slv_from_cl16(const void* x_bf16, float* y, int64_t N, int C, int Cp, int64_
  *   clip has a contrast stage: a first launch writes the mean gray value of every frame of those clips as they stand in
  *   front of their contrast stage (float64 sum in a fixed order, rounded once), the second launch writes out.  Every
  *   product and sum of the stages is rounded separately like torch's on the CPU; two calls give the same bits.
+ * slv_clip_sample_augment / slv_clip_sample_augment_color are the two above with datasets/decoder.py:21-38
+ *   (temporal_sampling) folded into the read: frames_u8 holds whole decoded videos, the first word of a clip's desc row
+ *   is the byte offset of its VIDEO (n_frames x H x W x 3 uint8; several clips may name the same video: the two clips
+ *   of a dual_data sample, the views of a test video), and output frame t of clip b is frame fidx[b * T + t] of that
+ *   video.  fidx: B x T int32 on the device; fidx_host: the same table on the host; n_frames_host: B int64 on the host,
+ *   the length of the video each clip names.  Any entry outside [0, n_frames_host[b]) is an error and nothing is
+ *   launched.  Per pixel the arithmetic is that of slv_clip_augment[_color], and so is the fixed-order float64 frame
+ *   mean: for the same frames the outputs are the same bits.  Grid order and why: csrc/input.hip, clip_augment_kernel.
  * slv_logfbank replaces datasets/audio_utils.py:46-72 (python_speech_features.logfbank 0.6 with winfunc = ones,
  *   lowfreq 0, highfreq samplerate/2) for B clips: wav_i16 [B][wav_stride] int16 PCM, start_i64[b] first sample of
  *   the clip's window, volume_f64 nullable per-clip factor (audio_utils.py:42-43), slen samples per window;
@@ -495,6 +503,13 @@ int slv_clip_augment(const void* frames_u8, const int64_t* desc, float* out, int
 int slv_clip_augment_color(const void* frames_u8, const int64_t* desc, const void* color, const void* color_host,
                            float* frame_mean_ws, float* out, int B, int T, int S, const float* mean3,
                            const float* std3, slv_stream_t stream);
+int slv_clip_sample_augment(const void* frames_u8, const int64_t* desc, const int32_t* fidx, const int32_t* fidx_host,
+                            const int64_t* n_frames_host, float* out, int B, int T, int S, const float* mean3,
+                            const float* std3, slv_stream_t stream);
+int slv_clip_sample_augment_color(const void* frames_u8, const int64_t* desc, const int32_t* fidx,
+                                  const int32_t* fidx_host, const int64_t* n_frames_host, const void* color,
+                                  const void* color_host, float* frame_mean_ws, float* out, int B, int T, int S,
+                                  const float* mean3, const float* std3, slv_stream_t stream);
 int32_t slv_logfbank_frames(int slen, int frame_len, int frame_step);   /* sigproc.framesig frame count; -1 on bad sizes */
 int slv_logfbank(const void* wav_i16, const int64_t* start_i64, const double* volume_f64, int64_t wav_stride, int B,
                  int slen, int frame_len, int frame_step, int nfft, int nfilt, const double* twiddle_f64,

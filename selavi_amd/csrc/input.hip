@@ -7,6 +7,9 @@
 //   slv_clip_augment_color  the same plus color_jitter (:273-363) and grayscale (:251-270, :498-500): the stage chain
 //                      runs in registers behind the sampling; a contrast stage needs the mean gray value of each frame
 //                      first, which a pass of its own recomputes from the uint8 source (no float clip is read back).
+//   slv_clip_sample_augment[_color]  the same two, reading frame fidx[b][t] of a whole decoded video instead of frame t
+//                      of a T-frame clip (datasets/decoder.py:21-38 temporal_sampling folded into the read): no gathered
+//                      copy of the clip is written and read back, and several output clips may name one resident video.
 //   slv_logfbank       datasets/audio_utils.py:46-72 -> python_speech_features.logfbank (0.6): pre-emphasis, framing
 //                      (rectangular window), |rfft|^2/nfft, triangular mel filterbank, log -- in float64 like numpy,
 //                      stored as float32 [B][1][nfilt][frames].
@@ -64,18 +67,35 @@ __device__ __forceinline__ void sample_px(const unsigned char* __restrict__ f, i
   }
 }
 
-// grid (ceil(S*S/256), T, B); thread = one output pixel, all three channels
+// Thread = one output pixel, all three channels.  kTable = false (slv_clip_augment): grid (ceil(S*S/256), T, B), clip b
+// holds exactly T frames and output frame t reads frame t.  kTable = true (slv_clip_sample_augment): clip b names a whole
+// video and output frame t reads frame fidx[b * T + t] of it (checked against the video's length on the host).
+//
+// Grid order with a table: (ceil(S*S/256), B, T), the clip index in front of the frame slot.  Output clips that share a
+// video are neighbours in b (the two clips of a dual_data sample, the spatial crops of one test view), and the crops of
+// one view read the SAME source frame in slot t.  With b next to the tile index their workgroups are dispatched back to
+// back (49 tiles apart at crop 112) and are resident together, so the second and third crop find the frame's bytes in
+// the L2 of the XCD they land on or in the Infinity Cache; in the (T, B) order of the clip kernel they would be a whole
+// clip (T x tiles workgroups) apart.  Workgroups are dealt round-robin over the eight XCDs, so every XCD's L2 fetches a
+// frame once either way; the order decides only how soon the re-reads follow.  The four bilinear taps stay single-byte
+// loads: a pixel is three bytes, so a tap is never aligned for a wider access, neighbouring lanes read neighbouring
+// pixels of the same two source rows (the wave's loads fall into the same few cache lines), and per thread they stand
+// next to 24 IEEE divides and three float stores.
+template <bool kTable>
 __global__ __launch_bounds__(256) void clip_augment_kernel(const unsigned char* __restrict__ src,
-                                                           const ClipDesc* __restrict__ desc, float* __restrict__ out,
+                                                           const ClipDesc* __restrict__ desc,
+                                                           const int* __restrict__ fidx, float* __restrict__ out,
                                                            int T, int S, float m0, float m1, float m2, float s0,
                                                            float s1, float s2) {
   const int p = blockIdx.x * 256 + threadIdx.x;
   if (p >= S * S) return;
-  const int oy = p / S, ox = p - oy * S, t = blockIdx.y, b = blockIdx.z;
+  const int oy = p / S, ox = p - oy * S;
+  const int t = kTable ? blockIdx.z : blockIdx.y, b = kTable ? blockIdx.y : blockIdx.z;
   const ClipDesc d = desc[b];
   const int H = (int)d.H, W = (int)d.W;
   const int ry = oy + (int)d.y_off, rx = (d.flip ? S - 1 - ox : ox) + (int)d.x_off;
-  const unsigned char* f = src + d.src_off + (size_t)t * H * W * 3;
+  const int fr = kTable ? fidx[(size_t)b * T + t] : t;
+  const unsigned char* f = src + d.src_off + (size_t)fr * H * W * 3;
   const float mean[3] = {m0, m1, m2}, stdv[3] = {s0, s1, s2};
   float* o = out + (((size_t)b * 3) * T + t) * S * S + p;
   const size_t cstride = (size_t)T * S * S;
@@ -125,10 +145,13 @@ __device__ __forceinline__ void color_stages(float (&px)[3], const ColorDesc& cd
 // pixels i, i + GM_THREADS, ... and the partial sums go through a fixed tree, so every launch gives the same bits.
 // 1024 threads: a (clip, frame) is one workgroup, so a batch of 16 x 16 is one workgroup per CU, and the sampling is
 // ALU-bound per pixel (24 IEEE divides) -- four waves per SIMD instead of one to overlap it with the byte loads.
+// kTable: the frame comes through the frame table, as in clip_augment_kernel; the sum and its order are the same.
 constexpr int GM_THREADS = 1024;
+template <bool kTable>
 __global__ __launch_bounds__(GM_THREADS) void clip_gray_mean_kernel(const unsigned char* __restrict__ src,
                                                              const ClipDesc* __restrict__ desc,
                                                              const ColorDesc* __restrict__ color,
+                                                             const int* __restrict__ fidx,
                                                              float* __restrict__ frame_mean, int T, int S, float m0,
                                                              float m1, float m2, float s0, float s1, float s2) {
   __shared__ double part[GM_THREADS];
@@ -140,7 +163,8 @@ __global__ __launch_bounds__(GM_THREADS) void clip_gray_mean_kernel(const unsign
   if (k < 0) return;                             // block-uniform: no barrier has been reached
   const ClipDesc d = desc[b];
   const int H = (int)d.H, W = (int)d.W, nh = (int)d.nh, nw = (int)d.nw;
-  const unsigned char* f = src + d.src_off + (size_t)t * H * W * 3;
+  const int fr = kTable ? fidx[(size_t)b * T + t] : t;
+  const unsigned char* f = src + d.src_off + (size_t)fr * H * W * 3;
   const float mean[3] = {m0, m1, m2}, stdv[3] = {s0, s1, s2};
   double acc = 0.0;
   for (int p = tid; p < S * S; p += GM_THREADS) {
@@ -160,22 +184,26 @@ __global__ __launch_bounds__(GM_THREADS) void clip_gray_mean_kernel(const unsign
   if (tid == 0) frame_mean[(size_t)b * T + t] = (float)(part[0] / (double)((long long)S * S));
 }
 
-// pass 2 -- grid (ceil(S*S/256), T, B) like clip_augment_kernel: sampling, the whole chain and the grayscale flag in
-// registers, one write of the clip
+// pass 2 -- the grid of clip_augment_kernel (with a table: its (tiles, B, T) order): sampling, the whole chain and the
+// grayscale flag in registers, one write of the clip
+template <bool kTable>
 __global__ __launch_bounds__(256) void clip_augment_color_kernel(const unsigned char* __restrict__ src,
                                                                  const ClipDesc* __restrict__ desc,
                                                                  const ColorDesc* __restrict__ color,
+                                                                 const int* __restrict__ fidx,
                                                                  const float* __restrict__ frame_mean,
                                                                  float* __restrict__ out, int T, int S, float m0,
                                                                  float m1, float m2, float s0, float s1, float s2) {
   const int p = blockIdx.x * 256 + threadIdx.x;
   if (p >= S * S) return;
-  const int oy = p / S, ox = p - oy * S, t = blockIdx.y, b = blockIdx.z;
+  const int oy = p / S, ox = p - oy * S;
+  const int t = kTable ? blockIdx.z : blockIdx.y, b = kTable ? blockIdx.y : blockIdx.z;
   const ClipDesc d = desc[b];
   const ColorDesc cd = color[b];
   const int H = (int)d.H, W = (int)d.W;
   const int ry = oy + (int)d.y_off, rx = (d.flip ? S - 1 - ox : ox) + (int)d.x_off;
-  const unsigned char* f = src + d.src_off + (size_t)t * H * W * 3;
+  const int fr = kTable ? fidx[(size_t)b * T + t] : t;
+  const unsigned char* f = src + d.src_off + (size_t)fr * H * W * 3;
   const float mean[3] = {m0, m1, m2}, stdv[3] = {s0, s1, s2};
   float px[3];
   sample_px(f, H, W, (int)d.nh, (int)d.nw, ry, rx, mean, stdv, px);
@@ -254,49 +282,129 @@ __global__ __launch_bounds__(256) void logfbank_kernel(const short* __restrict__
 
 extern "C" {
 
+// the launches behind the four video entry points; fidx == nullptr: the clip kernels (frame t of a T-frame clip)
+// (fn: the entry point's name, for the error text)
+static int launch_clip_augment(const char* fn, const void* frames_u8, const int64_t* desc, const int32_t* fidx, float* out,
+                               int B, int T, int S, const float* mean3, const float* std3, void* stream) {
+  using namespace slv;
+  const unsigned tiles = cdiv((long)S * S, 256);
+  if (fidx) {
+    hipLaunchKernelGGL(clip_augment_kernel<true>, dim3(tiles, B, T), dim3(256), 0, (hipStream_t)stream,
+                       (const unsigned char*)frames_u8, (const ClipDesc*)desc, (const int*)fidx, (float*)out, T, S,
+                       mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2]);
+  } else {
+    hipLaunchKernelGGL(clip_augment_kernel<false>, dim3(tiles, T, B), dim3(256), 0, (hipStream_t)stream,
+                       (const unsigned char*)frames_u8, (const ClipDesc*)desc, (const int*)nullptr, (float*)out, T, S,
+                       mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2]);
+  }
+  return launch_check(fn);
+}
+
+// the argument checks of the colour words (host copy); *any_contrast: whether pass 1 is needed
+// SLV_CHECK_ARG for the helpers below: the message names the entry point (fn), which has noted pending errors already
+#define SLV_CHECK_ARG_FN(cond, msg) \
+  do {                             \
+    if (!(cond)) return ::slv::fail(-2, "%s: bad argument: " msg, fn); \
+  } while (0)
+static int check_color_host(const char* fn, const void* color_host, int B, bool* any_contrast) {
+  using namespace slv;
+  const ColorDesc* ch = (const ColorDesc*)color_host;
+  *any_contrast = false;
+  for (int b = 0; b < B; ++b) {
+    int n_contrast = 0;
+    for (int i = 0; i < 3; ++i) {
+      SLV_CHECK_ARG_FN(ch[b].stage[i] >= CJ_NONE && ch[b].stage[i] <= CJ_SATURATION, "unknown stage code");
+      n_contrast += ch[b].stage[i] == CJ_CONTRAST;
+    }
+    SLV_CHECK_ARG_FN(n_contrast <= 1, "more than one contrast stage in a clip");
+    *any_contrast = *any_contrast || n_contrast;
+  }
+  return 0;
+}
+
+static int launch_clip_augment_color(const char* fn, const void* frames_u8, const int64_t* desc, const void* color, const int32_t* fidx,
+                                     bool any_contrast, float* frame_mean_ws, float* out, int B, int T, int S,
+                                     const float* mean3, const float* std3, void* stream) {
+  using namespace slv;
+  const unsigned tiles = cdiv((long)S * S, 256);
+  if (any_contrast) {
+    if (fidx)
+      hipLaunchKernelGGL(clip_gray_mean_kernel<true>, dim3(T, B), dim3(GM_THREADS), 0, (hipStream_t)stream,
+                         (const unsigned char*)frames_u8, (const ClipDesc*)desc, (const ColorDesc*)color,
+                         (const int*)fidx, frame_mean_ws, T, S, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2]);
+    else
+      hipLaunchKernelGGL(clip_gray_mean_kernel<false>, dim3(T, B), dim3(GM_THREADS), 0, (hipStream_t)stream,
+                         (const unsigned char*)frames_u8, (const ClipDesc*)desc, (const ColorDesc*)color,
+                         (const int*)nullptr, frame_mean_ws, T, S, mean3[0], mean3[1], mean3[2], std3[0], std3[1],
+                         std3[2]);
+    if (int rc = launch_check(fn)) return rc;
+  }
+  if (fidx)
+    hipLaunchKernelGGL(clip_augment_color_kernel<true>, dim3(tiles, B, T), dim3(256), 0, (hipStream_t)stream,
+                       (const unsigned char*)frames_u8, (const ClipDesc*)desc, (const ColorDesc*)color, (const int*)fidx,
+                       frame_mean_ws, (float*)out, T, S, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2]);
+  else
+    hipLaunchKernelGGL(clip_augment_color_kernel<false>, dim3(tiles, T, B), dim3(256), 0, (hipStream_t)stream,
+                       (const unsigned char*)frames_u8, (const ClipDesc*)desc, (const ColorDesc*)color,
+                       (const int*)nullptr, frame_mean_ws, (float*)out, T, S, mean3[0], mean3[1], mean3[2], std3[0],
+                       std3[1], std3[2]);
+  return launch_check(fn);
+}
+
+// every entry of the host copy of the frame table against the length of the video its clip names
+static int check_frame_table(const char* fn, const int32_t* fidx_host, const int64_t* n_frames_host, int B, int T) {
+  for (int b = 0; b < B; ++b) {
+    SLV_CHECK_ARG_FN(n_frames_host[b] > 0, "a video without frames");
+    for (int t = 0; t < T; ++t) {
+      const int32_t i = fidx_host[(size_t)b * T + t];
+      SLV_CHECK_ARG_FN(i >= 0 && (int64_t)i < n_frames_host[b], "frame index outside the video");
+    }
+  }
+  return 0;
+}
+#undef SLV_CHECK_ARG_FN
+
 int slv_clip_augment(const void* frames_u8, const int64_t* desc, float* out, int B, int T, int S,
                      const float* mean3, const float* std3, void* stream) {
-  using namespace slv;
   SLV_CHECK_ARG(frames_u8 && desc && out && mean3 && std3, "null pointer");
   SLV_CHECK_ARG(B > 0 && T > 0 && S > 0 && B <= 65535 && T <= 65535, "bad sizes");
-  dim3 grid(cdiv((long)S * S, 256), T, B);
-  hipLaunchKernelGGL(clip_augment_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const unsigned char*)frames_u8,
-                     (const ClipDesc*)desc, (float*)out, T, S, mean3[0], mean3[1], mean3[2], std3[0], std3[1],
-                     std3[2]);
-  SLV_LAUNCH_CHECK();
-  return 0;
+  return launch_clip_augment(__func__, frames_u8, desc, nullptr, out, B, T, S, mean3, std3, stream);
 }
 
 int slv_clip_augment_color(const void* frames_u8, const int64_t* desc, const void* color, const void* color_host,
                            float* frame_mean_ws, float* out, int B, int T, int S, const float* mean3,
                            const float* std3, void* stream) {
-  using namespace slv;
   SLV_CHECK_ARG(frames_u8 && desc && color && color_host && out && mean3 && std3, "null pointer");
   SLV_CHECK_ARG(B > 0 && T > 0 && S > 0 && B <= 65535 && T <= 65535, "bad sizes");
-  const ColorDesc* ch = (const ColorDesc*)color_host;
   bool any_contrast = false;
-  for (int b = 0; b < B; ++b) {
-    int n_contrast = 0;
-    for (int i = 0; i < 3; ++i) {
-      SLV_CHECK_ARG(ch[b].stage[i] >= CJ_NONE && ch[b].stage[i] <= CJ_SATURATION, "unknown stage code");
-      n_contrast += ch[b].stage[i] == CJ_CONTRAST;
-    }
-    SLV_CHECK_ARG(n_contrast <= 1, "more than one contrast stage in a clip");
-    any_contrast = any_contrast || n_contrast;
-  }
+  if (int rc = check_color_host(__func__, color_host, B, &any_contrast)) return rc;
   SLV_CHECK_ARG(!any_contrast || frame_mean_ws, "a contrast stage needs the B x T frame-mean workspace");
-  if (any_contrast) {
-    hipLaunchKernelGGL(clip_gray_mean_kernel, dim3(T, B), dim3(GM_THREADS), 0, (hipStream_t)stream,
-                       (const unsigned char*)frames_u8, (const ClipDesc*)desc, (const ColorDesc*)color, frame_mean_ws, T,
-                       S, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2]);
-    SLV_LAUNCH_CHECK();
-  }
-  dim3 grid(cdiv((long)S * S, 256), T, B);
-  hipLaunchKernelGGL(clip_augment_color_kernel, grid, dim3(256), 0, (hipStream_t)stream,
-                     (const unsigned char*)frames_u8, (const ClipDesc*)desc, (const ColorDesc*)color, frame_mean_ws,
-                     (float*)out, T, S, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2]);
-  SLV_LAUNCH_CHECK();
-  return 0;
+  return launch_clip_augment_color(__func__, frames_u8, desc, color, nullptr, any_contrast, frame_mean_ws, out, B, T, S, mean3,
+                                   std3, stream);
+}
+
+int slv_clip_sample_augment(const void* frames_u8, const int64_t* desc, const int32_t* fidx, const int32_t* fidx_host,
+                            const int64_t* n_frames_host, float* out, int B, int T, int S, const float* mean3,
+                            const float* std3, void* stream) {
+  SLV_CHECK_ARG(frames_u8 && desc && fidx && fidx_host && n_frames_host && out && mean3 && std3, "null pointer");
+  SLV_CHECK_ARG(B > 0 && T > 0 && S > 0 && B <= 65535 && T <= 65535, "bad sizes");
+  if (int rc = check_frame_table(__func__, fidx_host, n_frames_host, B, T)) return rc;
+  return launch_clip_augment(__func__, frames_u8, desc, fidx, out, B, T, S, mean3, std3, stream);
+}
+
+int slv_clip_sample_augment_color(const void* frames_u8, const int64_t* desc, const int32_t* fidx,
+                                  const int32_t* fidx_host, const int64_t* n_frames_host, const void* color,
+                                  const void* color_host, float* frame_mean_ws, float* out, int B, int T, int S,
+                                  const float* mean3, const float* std3, void* stream) {
+  SLV_CHECK_ARG(frames_u8 && desc && fidx && fidx_host && n_frames_host && color && color_host && out && mean3 && std3,
+                "null pointer");
+  SLV_CHECK_ARG(B > 0 && T > 0 && S > 0 && B <= 65535 && T <= 65535, "bad sizes");
+  if (int rc = check_frame_table(__func__, fidx_host, n_frames_host, B, T)) return rc;
+  bool any_contrast = false;
+  if (int rc = check_color_host(__func__, color_host, B, &any_contrast)) return rc;
+  SLV_CHECK_ARG(!any_contrast || frame_mean_ws, "a contrast stage needs the B x T frame-mean workspace");
+  return launch_clip_augment_color(__func__, frames_u8, desc, color, fidx, any_contrast, frame_mean_ws, out, B, T, S, mean3, std3,
+                                   stream);
 }
 
 int32_t slv_logfbank_frames(int slen, int frame_len, int frame_step) {

@@ -68,3 +68,59 @@ class SyntheticFramesDataset(SyntheticRetrievalDataset):
         video, lab, clip, vid = super().__getitem__(i)
         frames = ((video[:, :, :self.H, :self.W] * 0.225 + 0.45) * 255.0).round().clamp(0, 255).to(torch.uint8)
         return frames.permute(1, 2, 3, 0).contiguous(), lab, clip, vid
+
+
+class SyntheticVideoDataset(SyntheticRetrievalDataset):
+    """Whole decoded videos, what a decoder hands over before any temporal sampling: item ``i`` is sample
+    ``i % clips_per_video`` of video ``vid_idx = i // clips_per_video`` (the reference's AVideoDataset lists every video
+    num_clips times, AVideoDataset.py:296-306) -> ``(video[N,H,W,3] uint8, fps, label, spatial_temporal_idx, vid_idx)``,
+    with ``with_audio`` -> ``(video, wav int16 [n], fps, label, spatial_temporal_idx, vid_idx)``.  Lengths, frame sizes
+    (landscape and portrait) and frame rates differ from video to video; the pixels are the class / video patterns of
+    SyntheticRetrievalDataset, so the sets are learnable.  ``decoded_videos`` tells a driver to cut its clips with
+    datasets.av_batcher.DecodedAVBatcher; ``collate`` keeps one copy of a video that several items of a batch name."""
+    decoded_videos = True
+
+    def __init__(self, n_videos=16, clips_per_video=1, min_frames=12, max_frames=40, S=40, n_classes=8, seed=31,
+                 with_audio=False, aud_sample_rate=48000):
+        super().__init__(n_videos=n_videos, clips_per_video=clips_per_video, T=max_frames, S=S * 3 // 2,
+                         n_classes=n_classes, seed=seed)
+        g = torch.Generator().manual_seed(seed + 77)
+        self.n_frames = torch.randint(min_frames, max_frames + 1, (n_videos,), generator=g).tolist()
+        self.fps = [(24.0, 25.0, 29.97, 30.0)[k] for k in torch.randint(0, 4, (n_videos,), generator=g).tolist()]
+        sizes = ((S * 5 // 4, S * 3 // 2), (S * 3 // 2, S * 5 // 4), (S * 5 // 4, S * 5 // 4))
+        self.sizes = [sizes[k] for k in torch.randint(0, 3, (n_videos,), generator=g).tolist()]
+        self.with_audio, self.aud_sample_rate = with_audio, aud_sample_rate
+
+    def video(self, vid):
+        lab = self._labels[vid]
+        N, (H, W) = self.n_frames[vid], self.sizes[vid]
+        g = torch.Generator().manual_seed((self.seed * 1000003 + vid) * 7 + 3)
+        x = (self._pattern(9176 + lab, 1.0) + self._pattern((self.seed * 1000003 + vid) * 7 + 2, 0.5))[:, :N, :H, :W]
+        x = x + 0.5 * torch.randn(3, N, H, W, generator=g)
+        return ((x * 0.225 + 0.45) * 255.0).round().clamp(0, 255).to(torch.uint8).permute(1, 2, 3, 0).contiguous()
+
+    def wav(self, vid):
+        seconds = self.n_frames[vid] / self.fps[vid] + 1.5          # longer than the video by more than one window
+        g = torch.Generator().manual_seed((self.seed * 1000003 + vid) * 7 + 4)
+        return (torch.randn(int(seconds * self.aud_sample_rate), generator=g) * 3000).to(torch.int16)
+
+    def __getitem__(self, i):
+        vid, clip = divmod(int(i), self.clips_per_video)
+        head = (self.video(vid), self.wav(vid)) if self.with_audio else (self.video(vid),)
+        return head + (self.fps[vid], self._labels[vid], clip, vid)
+
+    @staticmethod
+    def collate(items):
+        """-> (videos, [wavs,] fps, video_of, labels, spatial_temporal_idx, vid_idx): the first lists hold one entry per
+        distinct video of the batch, ``video_of`` maps each item to its entry, the last three are int64 tensors."""
+        slot, cols = {}, [[] for _ in range(len(items[0]) - 3)]
+        video_of = []
+        for it in items:
+            vid = it[-1]
+            if vid not in slot:
+                slot[vid] = len(slot)
+                for c, x in zip(cols, it[:-3]):
+                    c.append(x)
+            video_of.append(slot[vid])
+        tail = [torch.tensor([it[k] for it in items], dtype=torch.int64) for k in (-3, -2, -1)]
+        return (*cols, video_of, *tail)

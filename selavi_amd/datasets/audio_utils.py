@@ -44,8 +44,13 @@ def window(n_samples, fr_sec, num_sec=1, sample_rate=48000, use_temporal_jitteri
     return fr_aud
 
 
-def get_spec_batch(wav, starts, num_sec=1, sample_rate=48000, aud_spec_type=1, volumes=None, z_normalize=False):
+def get_spec_batch(wav, starts, num_sec=1, sample_rate=48000, aud_spec_type=1, volumes=None, z_normalize=False,
+                   rows=None, lengths=None):
     """wav: B x n int16 (device); starts: B first-sample indices; volumes: optional B factors.
+    rows: None, or per output clip the row of ``wav`` its window is cut from (wav: R x n; several clips may share a
+    recording: the two clips of a dual_data sample, the views of a test video).
+    lengths: None, or per row of ``wav`` its true number of samples where the rows are padded to a common n; every
+    window must then lie inside its row's true length (without it only the padded length n is checked).
     -> B x 1 x nfilt x frames float32 (frames = 99 for one second)."""
     assert wav.dtype == torch.int16 and wav.dim() == 2 and wav.is_cuda and wav.is_contiguous()
     B, n = wav.shape
@@ -53,6 +58,18 @@ def get_spec_batch(wav, starts, num_sec=1, sample_rate=48000, aud_spec_type=1, v
     starts = np.asarray(starts, dtype=np.int64)
     if (starts < 0).any() or (starts + slen > n).any():
         raise ValueError("audio window outside the recording")
+    stride = n
+    if rows is None and lengths is not None:
+        raise ValueError("lengths goes with rows")
+    if rows is not None:                       # clip b reads row rows[b]: absolute starts, no per-clip stride
+        rows = np.asarray(rows, dtype=np.int64)
+        if rows.shape != starts.shape or (rows < 0).any() or (rows >= B).any():
+            raise ValueError("one row of wav per audio window")
+        if lengths is not None:
+            lengths = np.asarray(lengths, dtype=np.int64)
+            if lengths.shape != (B,) or (lengths > n).any() or (starts + slen > lengths[rows]).any():
+                raise ValueError("audio window outside the recording")
+        starts, stride, B = rows * n + starts, 0, len(starts)
     nfilt = 40 if aud_spec_type == 1 else 257
     frame_len, frame_step = _round_half_up(WINLEN * sample_rate), _round_half_up(WINSTEP * sample_rate)
     frames = C.slv_logfbank_frames(slen, frame_len, frame_step)
@@ -60,7 +77,7 @@ def get_spec_batch(wav, starts, num_sec=1, sample_rate=48000, aud_spec_type=1, v
     st = torch.from_numpy(starts).to(wav.device)
     vol = None if volumes is None else torch.as_tensor(np.asarray(volumes, dtype=np.float64)).to(wav.device)
     out = torch.empty((B, 1, nfilt, frames), dtype=torch.float32, device=wav.device)
-    C.slv_logfbank(ptr(wav), ptr(st), ptr(vol), n, B, slen, frame_len, frame_step, NFFT, nfilt, ptr(tw), ptr(bins),
+    C.slv_logfbank(ptr(wav), ptr(st), ptr(vol), stride, B, slen, frame_len, frame_step, NFFT, nfilt, ptr(tw), ptr(bins),
                    PREEMPH, int(bool(z_normalize)), ptr(out), stream())
     return out
 

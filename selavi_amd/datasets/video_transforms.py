@@ -8,6 +8,10 @@ frames once and writes the float32 C x T x S x S clip -- for a whole batch per l
 Colour jitter and grayscale (:273-363, :491-500) ride on the same kernel (slv_clip_augment_color): their draws are made
 by sample_color_params, again with the reference's generator calls, and ClipAugmenter is the per-batch callable that
 draws for every clip what the reference's worker would draw for it.
+
+clip_sample_augmentation_batch is the same step for callers that hold whole decoded videos: a B x T table of frame
+indices (datasets/decoder.py: frame_indices) goes up with the descriptors and slv_clip_sample_augment[_color] reads
+those frames straight from the videos, so temporal_sampling's gathered copy is never made.
 """
 import math
 
@@ -157,6 +161,84 @@ def clip_augmentation_batch(clips, params, crop_size, out=None, color=None):
         ws = torch.empty((B, T), dtype=torch.float32, device=buf.device)
     C.slv_clip_augment_color(ptr(buf), ptr(dev), ptr(dev) + desc.nbytes, words.ctypes.data, ptr(ws), ptr(out), B, T,
                              crop_size, _MEAN.ctypes.data, _STD.ctypes.data, stream())
+    return out
+
+
+def _video_layout(videos):
+    """-> (base pointer, device, per video (byte offset from the base, N, H, W)).
+    A list of tensors is addressed in place: the offsets are the distances of the tensors' data pointers from the first
+    one's (the device address space is flat), so no packed copy of the videos is made.  ``(buf, offsets, shapes)``: one
+    flat uint8 device buffer, the byte offset of each video in it and its (N, H, W)."""
+    if isinstance(videos, tuple):
+        buf, offs, shapes = videos
+        assert torch.is_tensor(buf) and buf.dtype == torch.uint8 and buf.dim() == 1 and buf.is_cuda
+        if len(offs) != len(shapes):
+            raise ValueError("one offset and one (N, H, W) per video")
+        lay = []
+        for o, (N, H, W) in zip(offs, shapes):
+            if o < 0 or N <= 0 or o + N * H * W * 3 > buf.numel():
+                raise ValueError("a video lies outside the frame buffer")
+            lay.append((int(o), int(N), int(H), int(W)))
+        return ptr(buf), buf.device, lay
+    videos = list(videos)
+    lay = []
+    for v in videos:
+        assert v.dtype == torch.uint8 and v.dim() == 4 and v.shape[-1] == 3 and v.is_cuda and v.shape[0] > 0
+        assert v.device == videos[0].device
+        lay.append((ptr(v) - ptr(videos[0]), v.shape[0], v.shape[1], v.shape[2]))
+    return ptr(videos[0]), videos[0].device, lay
+
+
+def clip_sample_augmentation_batch(videos, frame_idx, params, crop_size, out=None, color=None, video_of=None):
+    """temporal_sampling + clip_augmentation in one launch chain, from whole decoded videos.
+
+    videos: list of uint8 device tensors N_i x H_i x W_i x 3, or ``(buf, offsets, shapes)`` (see _video_layout).
+    frame_idx: B x T integers (array, tensor or rows), the frames of each output clip inside ITS video.
+    video_of: per output clip the index of its video (default: clip b is cut from video b); several clips may name one
+    video.  params / color / out: as in clip_augmentation_batch, per output clip.  -> B x 3 x T x S x S float32, equal
+    bit for bit to clip_augmentation_batch on the gathered clips."""
+    base, device, lay = _video_layout(videos)
+    if not torch.is_tensor(frame_idx) and len(frame_idx) and torch.is_tensor(frame_idx[0]):
+        frame_idx = torch.stack(list(frame_idx))
+    fidx = np.ascontiguousarray(frame_idx.cpu().numpy() if torch.is_tensor(frame_idx) else np.asarray(frame_idx))
+    if fidx.ndim != 2 or fidx.dtype.kind not in "iu":
+        raise ValueError("frame_idx: B x T integers")
+    B, T = fidx.shape
+    video_of = list(range(B)) if video_of is None else [int(v) for v in video_of]
+    if len(video_of) != B or len(params) != B or any(not 0 <= v < len(lay) for v in video_of):
+        raise ValueError("one video index and one spatial parameter set per output clip")
+    n_frames = np.array([lay[v][1] for v in video_of], dtype=np.int64)
+    if (fidx < 0).any() or (fidx >= n_frames[:, None]).any():
+        raise ValueError("frame index outside the video")
+    fidx = fidx.astype(np.int32)
+    desc = np.zeros((B, 8), dtype=np.int64)
+    for b, (v, (nh, nw, yo, xo, flip)) in enumerate(zip(video_of, params)):
+        if not (0 <= yo and yo + crop_size <= nh and 0 <= xo and xo + crop_size <= nw):
+            raise ValueError("crop window outside the resized frame")
+        off, _, H, W = lay[v]
+        desc[b] = (off, H, W, nh, nw, yo, xo, int(flip))
+    if color is not None and len(color) != B:
+        raise ValueError("one colour-parameter object (or None) per clip")
+    words = None if color is None else _color_desc(color)
+    # one upload: the spatial descriptors, the frame table, then (colour path) the colour words
+    parts = [desc.view(np.uint8).reshape(-1), fidx.view(np.uint8).reshape(-1)]
+    if words is not None:
+        parts.append(words.view(np.uint8).reshape(-1))
+    dev = torch.from_numpy(np.concatenate(parts)).to(device, non_blocking=False)
+    d_fidx = ptr(dev) + desc.nbytes
+    if out is None:
+        out = torch.empty((B, 3, T, crop_size, crop_size), dtype=torch.float32, device=device)
+    assert out.shape == (B, 3, T, crop_size, crop_size) and out.dtype == torch.float32 and out.is_cuda
+    if words is None:
+        C.slv_clip_sample_augment(base, ptr(dev), d_fidx, fidx.ctypes.data, n_frames.ctypes.data, ptr(out), B, T,
+                                  crop_size, _MEAN.ctypes.data, _STD.ctypes.data, stream())
+        return out
+    ws = None
+    if (words[:, :3] == CONTRAST).any():
+        ws = torch.empty((B, T), dtype=torch.float32, device=device)
+    C.slv_clip_sample_augment_color(base, ptr(dev), d_fidx, fidx.ctypes.data, n_frames.ctypes.data,
+                                    d_fidx + fidx.nbytes, words.ctypes.data, ptr(ws), ptr(out), B, T, crop_size,
+                                    _MEAN.ctypes.data, _STD.ctypes.data, stream())
     return out
 
 

@@ -11,7 +11,10 @@ data.SyntheticRetrievalDataset ones.  A dataset may hand out the video as augmen
 as decoded ``T x H x W x 3`` uint8 frames: those go through datasets.video_transforms.ClipAugmenter on the device
 (resize / crop / flip, ``--colorjitter``, ``--test_time_cj``), set up the way the reference sets up AVideoDataset
 (:176-207); a test set then carries the item's spatial-temporal index as the third item (AVideoDataset.py:370-380).
-``--dataset synthetic_uint8`` builds synthetic sets of that kind.
+``--dataset synthetic_uint8`` builds synthetic sets of that kind.  A dataset that declares ``decoded_videos = True`` hands
+out WHOLE decoded videos (data.SyntheticVideoDataset: ``--dataset synthetic_video``): its train clips and its
+``val_clips_per_video x num_spatial_crops`` test views are cut on the device by datasets.av_batcher.DecodedAVBatcher,
+set up like the reference's two AVideoDataset (:176-207), temporal sampling included.
 
 Divergences from the reference (it crashes or wastes work there; nothing observable changes):
   - train / evaluate take what they need as arguments instead of reading a global ``args``;
@@ -36,6 +39,7 @@ from torch import nn
 
 from . import nn as snn
 from . import ops, optim
+from .datasets.av_batcher import DecodedAVBatcher
 from .datasets.video_transforms import ClipAugmenter
 from .model import load_model
 from .utils import AverageMeter, load_model_parameters, save_checkpoint, video_accuracy
@@ -69,8 +73,9 @@ NUM_CLASSES = {
     'ucf101': 101,
     'synthetic': 11,
     'synthetic_uint8': 11,       # the synthetic sets as uint8 frames larger than the crop
+    'synthetic_video': 11,       # the synthetic sets as whole decoded videos of differing lengths and sizes
 }
-SYNTHETIC = ('synthetic', 'synthetic_uint8')
+SYNTHETIC = ('synthetic', 'synthetic_uint8', 'synthetic_video')
 
 
 def get_video_dim(vid_base_arch='r2plus1d_18'):
@@ -144,23 +149,62 @@ def _crop_size(args):
     return 128 if args.augtype == 1 else 224
 
 
+def _jitter_scales(crop):
+    """AVideoDataset.py:213-217."""
+    if crop in (112, 128):
+        return (128, 160)
+    if crop == 224:
+        return (256, 320)
+    return (crop, crop * 5 // 4)  # a synthetic size the reference has no rule for: the 128 rule, in proportion
+
+
 def build_augmenters(args):
     """The (train, test) ClipAugmenter for datasets that hand out uint8 frames, from the arguments the way the reference
     builds its two AVideoDataset (finetune_video.py:176-207, AVideoDataset.py:213-217,358-380): training draws scale,
     crop and flip (spatial_idx -1) with ``--colorjitter``; testing resizes the short side to the crop and takes view
     ``index % num_spatial_crops`` (given per clip in the call) with ``--test_time_cj``."""
     crop = _crop_size(args)
-    if crop in (112, 128):
-        scales = (128, 160)
-    elif crop == 224:
-        scales = (256, 320)
-    else:                        # a synthetic size the reference has no rule for: the 128 rule, in proportion
-        scales = (crop, crop * 5 // 4)
+    scales = _jitter_scales(crop)
     train_aug = ClipAugmenter(spatial_idx=-1, min_scale=scales[0], max_scale=scales[1], crop_size=crop,
                               colorjitter=args.colorjitter)
     test_aug = ClipAugmenter(spatial_idx=1, min_scale=crop, max_scale=crop, crop_size=crop,
                              colorjitter=args.test_time_cj)
     return train_aug, test_aug
+
+
+def build_batchers(args):
+    """The (train, test) DecodedAVBatcher for datasets of whole decoded videos, with the keywords of the reference's two
+    AVideoDataset (finetune_video.py:176-207)."""
+    crop = _crop_size(args)
+    train = DecodedAVBatcher(mode='train', num_frames=args.clip_len, sample_rate=args.steps_bet_clips,
+                             train_crop_size=crop, train_jitter_scles=_jitter_scales(crop),
+                             colorjitter=args.colorjitter, temp_jitter=True, center_crop=False, target_fps=30,
+                             decode_audio=False)
+    test = DecodedAVBatcher(mode='test', num_frames=args.clip_len, sample_rate=args.steps_bet_clips,
+                            test_crop_size=crop, num_spatial_crops=args.num_spatial_crops,
+                            num_ensemble_views=args.val_clips_per_video, colorjitter=args.test_time_cj,
+                            temp_jitter=True, target_fps=30, decode_audio=False)
+    return train, test
+
+
+class DecodedVideoLoader:
+    """A loader over a ``decoded_videos`` dataset (batches as its ``collate`` makes them) -> the batches train() and
+    evaluate() take: ``(clips B x 3 x T x S x S float32 on the device, target, spatial_temporal_idx, video_idx)``.  The
+    videos of a batch go to the device once each and the batcher cuts every item's clip from them."""
+
+    def __init__(self, loader, batcher):
+        self.loader, self.batcher, self.dataset = loader, batcher, loader.dataset
+
+    def __len__(self):
+        return len(self.loader)
+
+    def __iter__(self):
+        test = self.batcher.mode == 'test'
+        for videos, fps, video_of, target, st_idx, video_idx in self.loader:
+            videos = [v.cuda(non_blocking=True) for v in videos]
+            clips, _ = self.batcher(videos, fps, spatial_temporal_idx=st_idx.tolist() if test else None,
+                                    video_of=video_of)
+            yield clips, target, st_idx, video_idx
 
 
 def is_frames(video):
@@ -189,9 +233,20 @@ def _note_colorjitter_without_frames():
 
 
 def _synthetic_datasets(args):
-    from .data import SyntheticFramesDataset, SyntheticRetrievalDataset
+    from .data import SyntheticFramesDataset, SyntheticRetrievalDataset, SyntheticVideoDataset
     S = _crop_size(args)
     fold = int(args.fold)
+    if args.dataset == 'synthetic_video':
+        # videos from a little shorter than a clip's span (clamped indices) to a few spans long
+        lo, hi = max(args.clip_len * args.steps_bet_clips * 3 // 4, 2), args.clip_len * args.steps_bet_clips * 3
+        train = SyntheticVideoDataset(n_videos=args.synthetic_videos, clips_per_video=args.train_clips_per_video,
+                                      min_frames=lo, max_frames=hi, S=S, n_classes=NUM_CLASSES['synthetic'],
+                                      seed=1000 + fold)
+        test = SyntheticVideoDataset(n_videos=max(args.synthetic_videos // 2, 1),
+                                     clips_per_video=args.num_spatial_crops * args.val_clips_per_video,
+                                     min_frames=lo, max_frames=hi, S=S, n_classes=NUM_CLASSES['synthetic'],
+                                     seed=2000 + fold)
+        return train, test
     if args.dataset == 'synthetic_uint8':
         H, W = S * 5 // 4, S * 3 // 2                  # larger than the crop, landscape
         train = SyntheticFramesDataset(H, W, n_videos=args.synthetic_videos, clips_per_video=args.train_clips_per_video,
@@ -263,12 +318,20 @@ def main(args, writer=None, dataset=None, dataset_test=None):
                                       "(items (video, target, _, video_idx)) or use --dataset synthetic")
         dataset, dataset_test = _synthetic_datasets(args)
     logger.info("Creating data loaders")
-    data_loader = torch.utils.data.DataLoader(dataset, batch_size=args.batch_size, sampler=None,
-                                              num_workers=args.workers, pin_memory=True, drop_last=True, shuffle=True)
-    data_loader_test = torch.utils.data.DataLoader(dataset_test, batch_size=args.batch_size, sampler=None,
-                                                   num_workers=args.workers, pin_memory=True, drop_last=False)
-
     train_aug, test_aug = build_augmenters(args)
+    decoded = getattr(dataset, 'decoded_videos', False), getattr(dataset_test, 'decoded_videos', False)
+    data_loader = torch.utils.data.DataLoader(dataset, batch_size=args.batch_size, sampler=None,
+                                              num_workers=args.workers, pin_memory=True, drop_last=True, shuffle=True,
+                                              collate_fn=dataset.collate if decoded[0] else None)
+    data_loader_test = torch.utils.data.DataLoader(dataset_test, batch_size=args.batch_size, sampler=None,
+                                                   num_workers=args.workers, pin_memory=True, drop_last=False,
+                                                   collate_fn=dataset_test.collate if decoded[1] else None)
+    if any(decoded):             # whole decoded videos: the batchers draw and apply temporal sampling and augmentation
+        train_batcher, test_batcher = build_batchers(args)             # (--colorjitter / --test_time_cj included)
+        if decoded[0]:
+            data_loader, train_aug = DecodedVideoLoader(data_loader, train_batcher), None
+        if decoded[1]:
+            data_loader_test, test_aug = DecodedVideoLoader(data_loader_test, test_batcher), None
     nsc = args.num_spatial_crops
 
     optimizer = build_optimizer(args, model)
@@ -416,7 +479,8 @@ def evaluate(model, val_loader, epoch=0, writer=None, ds='hmdb51', augment=None,
 def parse_args(argv=None):
     """finetune_video.py:439-620: the reference's flags and defaults, plus ``synthetic`` as a dataset and the size of
     the synthetic sets (--synthetic_videos, --synthetic_crop); ``synthetic_uint8`` is the synthetic set handing out
-    uint8 frames larger than the crop, so that the device clip augmentation runs."""
+    uint8 frames larger than the crop, so that the device clip augmentation runs; ``synthetic_video`` is the synthetic
+    set handing out whole decoded videos, so that the device temporal sampling runs too."""
     def str2bool(v):
         v = v.lower()
         if v in ('yes', 'true', 't', '1'):
@@ -431,7 +495,8 @@ def parse_args(argv=None):
     add = parser.add_argument
     # DATA
     add('--dataset', default='ucf101', type=str,
-        choices=['kinetics', 'vggsound', 'kinetics_sound', 'ave', 'ucf101', 'hmdb51', 'synthetic', 'synthetic_uint8'])
+        choices=['kinetics', 'vggsound', 'kinetics_sound', 'ave', 'ucf101', 'hmdb51', 'synthetic', 'synthetic_uint8',
+                 'synthetic_video'])
     add('--root_dir', type=str, default='/path/to/dataset')
     add('--fold', default='1,2,3', type=str)
     add('--clip_len', default=32, type=int)
